@@ -126,7 +126,71 @@ def parse():
                          "rounds 2-3)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="only check the rank launch / rendezvous (gloo, no GPU): every rank prints its rank and exits")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (see dump_outputs); that step "
+                         "then starts from the trainer state before the first step (restored untimed), so that the same arguments give "
+                         "it the same inputs, and the same outputs up to rounding, in every run")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.decode or a.fresh_batches):
+        ap.error("--dump-outputs needs the training step on the pre-built batch (no --decode, no --fresh-batches)")
+    return a
+
+
+DUMP_SAMPLE = 5000000       # elements per dumped array at most: three fp32 arrays of 20 MB + the loss stay under 64 MB
+
+
+def _trainer_tensors(trainer):
+    f = trainer.flat
+    return (f.param, f.m, f.v, trainer._state, trainer._flag, trainer._ctl)
+
+
+def trainer_state(trainer):
+    """What a training step reads besides the batch and the weights' derived copies: fp32 masters, Adam moments, the device-side
+    step counters and flags, the host-side dropout seed counter and torch's generators (host copies, taken before the first step)."""
+    from gtos_amd import ops
+    return {"tensors": [t.detach().cpu().clone() for t in _trainer_tensors(trainer)], "flat_steps": trainer.flat.steps,
+            "steps_issued": trainer.steps_issued, "seed": ops._seed_state[0], "cpu_rng": torch.get_rng_state(),
+            "cuda_rng": torch.cuda.get_rng_state()}
+
+
+def restore_trainer_state(trainer, s):
+    from gtos_amd import ops
+    torch.cuda.synchronize()
+    for dst, src in zip(_trainer_tensors(trainer), s["tensors"]):
+        dst.copy_(src)
+    trainer.flat.grad.zero_()
+    trainer.flat.steps, trainer.steps_issued, trainer._counters = s["flat_steps"], s["steps_issued"], None
+    trainer.flat.sync_mirror()                     # bf16 mirror and weight transposes from the restored masters
+    ops.set_seed(s["seed"])
+    torch.set_rng_state(s["cpu_rng"])
+    torch.cuda.set_rng_state(s["cuda_rng"])
+    torch.cuda.synchronize()
+
+
+def dump_outputs(out_dir, trainer, loss):
+    """What a caller of Trainer.step holds after the last timed step: its loss (NaN when the abnormal-loss rule discarded the batch)
+    and the updated parameters with their Adam moments, each in the model's named_parameters order.  An array of more than DUMP_SAMPLE
+    elements is cut to the same DUMP_SAMPLE positions (ascending, drawn with seed 0) in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    f = trainer.flat
+    offset = {n: (o, p.numel()) for n, p, o in f.entries}
+    spans = [offset[n] for n, p in trainer.model.named_parameters() if n in offset]
+    arrays = {"loss": np.array([np.nan if loss is None else loss], dtype=np.float64)}
+    pick = None
+    for name, buf in (("params", f.param), ("adam_m", f.m), ("adam_v", f.v)):
+        flat = buf.detach().cpu().numpy()
+        vec = np.concatenate([flat[o:o + k] for o, k in spans]).astype(np.float32, copy=False)
+        if vec.size > DUMP_SAMPLE:
+            if pick is None:
+                pick = np.sort(np.random.default_rng(0).choice(vec.size, DUMP_SAMPLE, replace=False))
+            vec = vec[pick]
+        arrays[name] = vec
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log("outputs of the last timed step written to", out_dir, {k: v.shape for k, v in arrays.items()})
 
 
 def cpu_model():
@@ -628,6 +692,8 @@ def main():
         batch = {k: v.to(dev) for k, v in batch.items()}
     log("batch", stats)
     ops.set_seed(19940117 + rank)
+    # --dump-outputs: the state before the first step, restored before the last timed step (see the timed loop)
+    start_state = trainer_state(trainer) if a.dump_outputs else None
     wait_s = [0.0]
 
     def next_batch():
@@ -682,18 +748,29 @@ def main():
     retries0 = torch.cuda.memory_stats(dev).get("num_alloc_retries", 0)
     t0 = time.perf_counter()
     pend = []
-    for _ in range(a.steps):
+    paused = 0.0
+    for i in range(a.steps):
+        if start_state is not None and i == a.steps - 1:
+            # --dump-outputs: the last timed step starts from the state before the first step, whatever the steps before it left
+            # (the step's fp32 atomic sums round differently from run to run, and every further training step amplifies that).
+            # The steps before it finish on the clock; the restore itself is not timed.
+            sync()
+            t_p = time.perf_counter()
+            restore_trainer_state(trainer, start_state)
+            paused = time.perf_counter() - t_p
         # the abnormal-loss rule and the lr schedule run on the device (gtos_step_control): no host read of the loss inside
         # the step; the values are read after the timed region
         pend.append(trainer.step(next_batch(), sync=False))
     sync()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
     losses = [p_.value() for p_ in pend]
     ms_ = torch.cuda.memory_stats(dev)
     # allocator view of the timed region: a retry = hipMalloc failed, the cache was flushed (device-wide sync) and the request repeated
     memory_info = {"peak_allocated_gb": round(ms_.get("allocated_bytes.all.peak", 0) / 2 ** 30, 1),
                    "peak_reserved_gb": round(ms_.get("reserved_bytes.all.peak", 0) / 2 ** 30, 1),
                    "alloc_retries_in_timed_region": int(ms_.get("num_alloc_retries", 0) - retries0)}
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, trainer, losses[-1])      # before the legs below train the model further
     my_elapsed = elapsed
     if feed is not None:
         done = asm_times[n_asm0:] or asm_times

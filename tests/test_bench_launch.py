@@ -59,3 +59,55 @@ def test_bench_defaults_are_the_library_defaults(monkeypatch):
     from gtos_amd import encoder
     assert a.relation_masks == "path" == encoder.MASK_SHARING
     assert a.gpus == 1 and a.config == "C2" and not a.graph_leg and not a.fresh_batches
+
+
+def _bench_module(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_rejects_zero_steps_and_dump_outside_the_training_step(monkeypatch, capsys):
+    import pytest
+    bench = _bench_module("bench_mod3")
+    for argv in (["--steps", "0"], ["--dump-outputs", "d", "--decode"], ["--dump-outputs", "d", "--fresh-batches"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit):
+            bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.steps == 7 and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_step_results_in_parameter_order(tmp_path, monkeypatch):
+    """bench.dump_outputs on a CPU FlatParams: loss, parameters and Adam moments as float arrays in named_parameters order (the flat
+    buffer's alignment padding left out), cut to the same seeded positions in every call once they exceed DUMP_SAMPLE, <= 64 MB."""
+    import types
+    import numpy as np
+    import torch
+    from gtos_amd.flat import FlatParams
+    bench = _bench_module("bench_mod4")
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(13, 7), torch.nn.Linear(7, 5))
+    flat = FlatParams(model)                          # CPU: views only, no kernels
+    flat.m.normal_()
+    flat.v.uniform_()
+    trainer = types.SimpleNamespace(flat=flat, model=model)
+    want = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    bench.dump_outputs(str(tmp_path / "full"), trainer, 2.5)
+    got = {k: np.load(str(tmp_path / "full" / (k + ".npy"))) for k in ("loss", "params", "adam_m", "adam_v")}
+    assert got["loss"].dtype == np.float64 and got["loss"].tolist() == [2.5]
+    assert got["params"].dtype == np.float32 and np.array_equal(got["params"], want)
+    where = {n: o for n, _, o in flat.entries}
+    m_want = np.concatenate([flat.m[where[n]:where[n] + p.numel()].numpy() for n, p in model.named_parameters()])
+    assert np.array_equal(got["adam_m"], m_want) and got["adam_v"].shape == want.shape
+    bench.dump_outputs(str(tmp_path / "skipped"), trainer, None)
+    assert np.isnan(np.load(str(tmp_path / "skipped" / "loss.npy"))).all()
+    assert 3 * 4 * bench.DUMP_SAMPLE + 8 < 64 * 10 ** 6                        # three fp32 arrays and the loss at the cap
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 40)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), trainer, 2.5)
+    s1, s2 = (np.load(str(tmp_path / d / "params.npy")) for d in ("s1", "s2"))
+    assert s1.shape == (40,) and np.array_equal(s1, s2) and np.isin(s1, want).all()

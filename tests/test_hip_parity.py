@@ -1462,6 +1462,27 @@ def _bench_line(args, env_extra=None, timeout=900):
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
 
+def test_bench_dump_outputs_repeat_whatever_the_warmup(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's loss, parameters and Adam moments as .npy files, the same up to rounding (the order of
+    the step's fp32 atomic sums) in two runs whose pre-warm and warm-up differ: that step starts from the state before the first step --
+    a missed restore would differ by whole training steps; `--steps` sets the timed steps of the result line."""
+    base = ["--config", "C1", "--steps", "3", "--no-cpu-baseline", "--no-masks-leg", "--no-loader-leg"]
+    runs = []
+    for i, extra in enumerate((["--warmup", "1", "--prewarm-seconds", "0"], ["--warmup", "2", "--prewarm-seconds", "1"])):
+        d = _bench_line(base + extra + ["--dump-outputs", str(tmp_path / str(i))], dict(GTOS_BENCH_NO_DETAIL="1"))
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - d["config"]["B_per_gpu"]) < 1e-6 * d["config"]["B_per_gpu"]
+        runs.append({k: np.load(str(tmp_path / str(i) / (k + ".npy"))) for k in ("loss", "params", "adam_m", "adam_v")})
+    total = 0
+    for k, v in runs[0].items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+        rel = float(np.linalg.norm(v.astype(np.float64) - runs[1][k]) / np.linalg.norm(v.astype(np.float64)))
+        print("dump %s: relative difference of the two runs %.3e" % (k, rel))
+        assert rel < {"loss": 1e-5, "params": 1e-6}.get(k, 1e-4), (k, rel)
+        total += v.nbytes
+    assert runs[0]["adam_m"].any() and runs[0]["adam_v"].any() and total <= 64 * 2 ** 20
+
+
 def test_bench_strong_scaling_two_ranks_on_one_gpu_functional():
     """`--scaling strong`: the batch is B graphs in TOTAL (generator/train.py:183 divides the batch budget by the world
     size), rank r holds graphs [r*B/N, (r+1)*B/N); per-rank timing and exposed all-reduce time are reported."""
