@@ -1364,8 +1364,25 @@ extern "C" int gtos_gemm_tn_batch(int n, const void* const* A, const int64_t* ld
         if (!A[j] || !B[j] || !C[j] || (uintptr_t)A[j] % 16 || (uintptr_t)B[j] % 16 || (uintptr_t)C[j] % 16) return -25;
         if (bias && bias[j] && (uintptr_t)bias[j] % 4) return -25;
     }
-    for (int j0 = 0; j0 < n; j0 += TN_MAX_JOBS) {
-        const int nj = n - j0 < TN_MAX_JOBS ? n - j0 : TN_MAX_JOBS;
+    // One launch takes up to TN_MAX_JOBS consecutive jobs whose dW footprints [C, C + ((M-1) ldc + N) * 4) bytes are pairwise disjoint: the
+    // MODE 2 epilogue is a plain read-add-write by the tile's one workgroup, so two jobs on the same bytes in one launch would race and lose a
+    // contribution (the same layer used twice, two backward passes before one flush, overlapping row / column blocks of one weight).  The
+    // first job that meets one already taken starts the next launch on the same stream, which runs after this one.  (A conservative byte
+    // interval test: interleaved column blocks of one matrix also split; that costs a launch, never a wrong sum.  The bias column sums are
+    // fp32 atomics and need no split.)
+    for (int j0 = 0, nj = 0; j0 < n; j0 += nj) {
+        nj = 0;
+        while (nj < TN_MAX_JOBS && j0 + nj < n) {
+            const int q = j0 + nj;
+            const uintptr_t lo = (uintptr_t)C[q], hi = lo + (uintptr_t)(((int64_t)(M[q] - 1) * ldc[q] + N[q]) * 4);
+            bool meets = false;
+            for (int p = j0; p < q && !meets; ++p) {
+                const uintptr_t plo = (uintptr_t)C[p], phi = plo + (uintptr_t)(((int64_t)(M[p] - 1) * ldc[p] + N[p]) * 4);
+                meets = lo < phi && plo < hi;
+            }
+            if (meets) break;
+            ++nj;
+        }
         TnBatch tb{};
         ColBatch cb{};
         int tiles = 0, blocks = 0, ncol = 0;

@@ -61,7 +61,7 @@ class FlatParams:
             k = p.numel()
             self.param[o:o + k].copy_(p.data.reshape(-1))
             p.data = self.param[o:o + k].view(p.shape)
-            p.grad = self.grad[o:o + k].view(p.shape)
+            _ops.attach_grad_view(p, self.grad[o:o + k].view(p.shape))
             if self.mirror is not None:
                 p._gtos_mirror = self.mirror[o:o + k].view(p.shape)
         # transposed bf16 mirror of every 2-D weight (the operand of dX = dY W as an NT product), refreshed by ONE launch

@@ -188,6 +188,14 @@ def flush_dw(device=None):
         del jobs
 
 
+def discard_dw(device=None):
+    """Drop the noted small weight gradients of ``device`` (all devices: None) without launching them: a backward that raised part-way
+    left them behind, and the next join_side() would add them to the next step's gradient."""
+    for dev in list(_DW_PENDING):
+        if device is None or dev == device:
+            del _DW_PENDING[dev]
+
+
 # The auxiliary stream has a price in memory: the caching allocator keeps one pool per stream, blocks freed on one stream never serve the
 # other, and the two pools peak at different moments of a step -- measured: C2 31 GB allocated, 94-99 GB reserved with the auxiliary
 # stream, 37 GB without (61.6 vs 62.1 ms per step); C5 93 GB allocated, 230-277 GB reserved with it (of 288 GB: one allocator retry from
@@ -366,12 +374,19 @@ def weight_t(param, w, rows=None):
     return t
 
 
+def attach_grad_view(p, view):
+    """Make ``view`` (fp32, contiguous: a view of a flat gradient bucket) the gradient of ``p`` and mark it as a bucket view: backward then
+    accumulates into it in place, and some of that work may wait for join_side().  Any other ``.grad`` goes through autograd."""
+    p.grad = view
+    p._gtos_grad_view = p.grad
+
+
 def _grad_target(p):
-    """Pre-allocated .grad (a view of the flat gradient bucket) to accumulate into, or None."""
+    """Pre-allocated .grad to accumulate into -- only while it is still the bucket view attach_grad_view() attached -- or None."""
     if not p.is_leaf:
         return None
     g = p.grad
-    if g is not None and g.dtype == torch.float32 and g.is_contiguous():
+    if g is not None and g is getattr(p, "_gtos_grad_view", None) and g.dtype == torch.float32 and g.is_contiguous():
         return g
     return None
 

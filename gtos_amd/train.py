@@ -38,6 +38,14 @@ def generator_segment_of(name):
     return len(GENERATOR_SEGMENTS)
 
 
+def discard_partial_step(flat):
+    """A step that raised between its forward and the optimizer: drop the small weight gradients its backward noted (ops.discard_dw) and
+    zero the bucket, so that nothing of the failed step reaches the next one."""
+    ops.discard_dw(flat.grad.device)
+    ops.join_side(flat.grad.device)
+    flat.grad.zero_()
+
+
 class SegmentBoundaryFn(torch.autograd.Function):
     """Identity on ``tensors``; its backward runs once the gradients of ALL of them are complete, i.e. when every
     autograd node downstream of the boundary has run -- the moment the parameters of segments <= ``seg`` hold their final
@@ -187,15 +195,20 @@ class Trainer:
             # is the bottleneck and never triggers when the host is (the event has long completed).
             while len(self._done_events) >= MAX_STEPS_AHEAD:
                 self._done_events.pop(0).synchronize()
-        loss = self.model(batch)
-        loss = loss if loss.dtype == torch.float32 else loss.float()
-        self._control(0, loss.detach())
-        if self.collective and self.steps_issued > self.warmup_steps:       # batches_acm <= steps_issued: never needed earlier
-            dist.all_reduce(self._flag, op=dist.ReduceOp.MAX)
-        self._control(1, loss.detach())
-        self.steps_issued += 1
-        loss.backward()
-        self.all_reduce_grads()
+        try:
+            loss = self.model(batch)
+            loss = loss if loss.dtype == torch.float32 else loss.float()
+            self._control(0, loss.detach())
+            if self.collective and self.steps_issued > self.warmup_steps:       # batches_acm <= steps_issued: never needed earlier
+                dist.all_reduce(self._flag, op=dist.ReduceOp.MAX)
+            self._control(1, loss.detach())
+            self.steps_issued += 1
+            loss.backward()
+            self.all_reduce_grads()
+        except BaseException:
+            discard_partial_step(self.flat)
+            self._works, self._launched = [], 0     # (data parallel, a rank that raised has left the collective sequence anyway)
+            raise
         self.flat.step(None, gscale=1.0 / self.world_size, max_norm=1.0, ctl=self._ctl)
         self.flat.zero_grad()
         res = PendingLoss(torch.cat([loss.detach().reshape(1), self._flag]))
@@ -258,12 +271,16 @@ class GraphedStep:
         # stream that is not being captured
         main, side = torch.cuda.current_stream(self._dev), ops.side_stream(self._dev)
         side.wait_stream(main)
-        loss = t.model(self.batch)
-        loss = loss if loss.dtype == torch.float32 else loss.float()
-        t._control(0, loss.detach())
-        t._control(1, loss.detach())
-        loss.backward()
-        ops.join_side()
+        try:
+            loss = t.model(self.batch)
+            loss = loss if loss.dtype == torch.float32 else loss.float()
+            t._control(0, loss.detach())
+            t._control(1, loss.detach())
+            loss.backward()
+            ops.join_side()
+        except BaseException:
+            discard_partial_step(t.flat)
+            raise
         t.flat.step(None, gscale=1.0, max_norm=1.0, ctl=t._ctl)
         t.flat.zero_grad()
         main.wait_stream(side)

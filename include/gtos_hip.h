@@ -250,8 +250,11 @@ int gtos_gru_weight_grads(int rows, int hs, int in_dim, int in_valid, const void
  * entries.  For job j:  C[j] [M[j], N[j]] (fp32, row stride ldc[j]) += A[j]^T B[j]  with A[j] [K[j], M[j]] = dY and B[j] [K[j], N[j]] = X (bf16,
  * row strides lda[j], ldb[j]), and, where bias != NULL and bias[j] != NULL,  bias[j][M[j]] (fp32) += column sums of A[j].  One workgroup per
  * 256x256 tile of one job over the job's whole K on the ping-pong TN kernel (no split-K: the tile has one writer, so the result is
- * deterministic), then one batched column-sum launch (fp32 atomics across row blocks).  M, N % 8 == 0, leading dimensions % 8 (ldc % 4),
- * A / B / C 16-byte aligned; anything else returns -22 / -25 and launches nothing. */
+ * deterministic), then one batched column-sum launch (fp32 atomics across row blocks).  Targets may repeat or overlap (the same layer used
+ * twice, two backward passes before one call, row / column blocks of one weight): a launch never holds two jobs whose byte ranges
+ * [C[j], C[j] + ((M[j]-1) ldc[j] + N[j]) * 4) intersect -- the first such job starts the next launch on the same stream, so every
+ * contribution lands.  M, N % 8 == 0, leading dimensions % 8 (ldc % 4), A / B / C 16-byte aligned; anything else returns -22 / -25 and
+ * launches nothing. */
 int gtos_gemm_tn_batch(int n, const void* const* A, const int64_t* lda, const int* M, const void* const* B, const int64_t* ldb, const int* N,
                        const int* K, float* const* C, const int64_t* ldc, float* const* bias, void* stream);
 

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import load_golden, sub, T, opt_mask
-from tests_support import SMALL_VOCAB, SMALL_GEN_ARGS
+from tests_support import SMALL_VOCAB, SMALL_GEN_ARGS, full_model_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -173,12 +173,13 @@ def test_small_weight_gradients_batched_equal_launched_in_place(monkeypatch):
         off = 0
         for w, b in ws:                                   # gradients land in views of a flat fp32 bucket, like FlatParams
             for t in (w, b):
-                t.grad = flat[off:off + t.numel()].view(t.shape)
+                ops.attach_grad_view(t, flat[off:off + t.numel()].view(t.shape))
                 off += t.numel()
         h = x0.to(dev()).to(torch.bfloat16)
         for w, b in ws:
             h = ops.linear(h, w, b)
         h.float().square().sum().backward()
+        assert bool(ops._DW_PENDING) == mode              # the batched path really noted its jobs (and the other one did not)
         ops.join_side()
         torch.cuda.synchronize()
         assert float(flat.abs().max()) > 0
@@ -688,27 +689,7 @@ def test_full_size_properties_c2_shape():
 
 # ------------------------------------------------------------------------------------------------ BASELINE configs vs the oracle
 def _full_model_pair(cfg_name, B, layers=None):
-    """Product Generator on the GPU and the pinned oracle on the CPU with identical weights (train.sh dims, dropout 0)."""
-    import copy
-    from gtos_amd import synth
-    from gtos_amd.config import default_vocabs, generator_args
-    from gtos_amd.generator import Generator
-    from oracle import gtos_oracle as O
-    cfg = dict(synth.CONFIGS[cfg_name])
-    if layers:
-        cfg["layers"] = layers
-    args = generator_args(cfg)
-    args["dropout"] = 0.0
-    depth = 256 if cfg["kind"] == "dep" else 32
-    torch.manual_seed(11)
-    ref = O.Generator({k: O.VocabSpec(v.size, 0) for k, v in default_vocabs().items()}, depth_size=depth, **args)
-    for p in ref.parameters():
-        if p.dim() == 1 or float(p.detach().abs().sum()) == 0:
-            p.data.add_(0.02 * torch.randn_like(p))
-    m = Generator(default_vocabs(), device=dev(), depth_size=depth, **args).to(dev())
-    m.load_state_dict(ref.state_dict())
-    batch, stats = synth.make_config_batch(cfg_name, B=B, padded=True)
-    return ref, m, batch, stats
+    return full_model_pair(dev(), cfg_name, B, layers)
 
 
 @pytest.mark.parametrize("cfg_name,B", [("C1", 8), ("C3", 3)])
