@@ -92,6 +92,16 @@ class DecodeLayer(nn.Module):
             outs, c = layer.step(outs, token_row, None if caches is None else caches[li], mem['inf_ext_kv'][li],
                                  mem['graph_padding_mask'])
             new_caches.append(c)
-        ll = self.token_generator(outs, None, mem['graph_padding_mask'], mem['cp_seq'], work=True,
-                                  align_kv=mem['align_kv'], tot_ext=mem['tot_ext'])
-        return ll, new_caches
+        return self._step_ll(outs, mem), new_caches
+
+    def step_into(self, probe, token_row, caches, t, mem):
+        """step() on preallocated caches (per inference layer [T_max,N,2d], row t written, rows [0,t] read; see
+        TransformerLayer.step_into).  Returns ll [1,N,V+ext]."""
+        outs = probe
+        for li, layer in enumerate(self.inference_core.layers):
+            outs = layer.step_into(outs, token_row, caches[li], t, mem['inf_ext_kv'][li], mem['graph_padding_mask'])
+        return self._step_ll(outs, mem)
+
+    def _step_ll(self, outs, mem):
+        return self.token_generator(outs, None, mem['graph_padding_mask'], mem['cp_seq'], work=True,
+                                    align_kv=mem['align_kv'], tot_ext=mem['tot_ext'])

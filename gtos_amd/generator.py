@@ -19,8 +19,8 @@ from .encoder import TokenEncoder, RelationEncoder
 from .decoder import DecodeLayer
 from .transformer import Transformer, SinusoidalPositionalEmbedding, SelfAttentionMask
 from .graph_transformer import GraphTransformer, set_compute_dtype
-from .search import Beam, beam_search
-from .vocab import lists_to_tensor, strings_to_char_tensor
+from .search import Beam, beam_search, beam_search_device
+from .vocab import PAD, UNK, STR, END, lists_to_tensor, strings_to_char_tensor
 
 
 class Generator(nn.Module):
@@ -138,9 +138,12 @@ class Generator(nn.Module):
         return out
 
     # ------------------------------------------------------------------------------------------------ inference
-    def work(self, data, beam_size, max_time_step, min_time_step=1):
+    def work(self, data, beam_size, max_time_step, min_time_step=1, search="host"):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
-        (``beam.get_k_best(k, alpha)``)."""
+        (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
+        step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU)."""
+        if search not in ("host", "device"):
+            raise ValueError("search must be 'host' or 'device', got %r" % (search,))
         with torch.no_grad():
             concept_repr, concept_mask, probe = self.encode_step(data, train=False)
             concept_repr = concept_repr.contiguous()
@@ -157,8 +160,72 @@ class Generator(nn.Module):
                 'align_kv': dec.token_generator.alignment_layer.project_kv(concept_repr),
             }
             beams = [Beam(beam_size, min_time_step, max_time_step) for _ in range(concept_repr.size(1))]
-            beam_search(self, beams, memory)
+            if search == "device":
+                beam_search_device(self, memory, beams)
+            else:
+                beam_search(self, beams, memory)
         return beams
+
+    # ---- fixed-slot decoding for gtos_amd.search.beam_search_device
+    def search_tables(self, local_idx2token, tot):
+        """Per batch, for every output id of the ll row [0, tot): its string class (0 plain, 1 <UNK>, 2 <END>), and the token id and
+        character row prepare_incremental_input builds for its string.  Ids < V (the predictable-token vocabulary) share one table,
+        kept across batches; ids in [V, tot) get one table per graph from local_idx2token (copy ids start at V, the reference's
+        data.py).  Returns a dict of device tensors plus the start (<STR>) and dead-slot (<PAD>) inputs."""
+        pv, tv, cv = self.vocabs['predictable_token'], self.vocabs['token'], self.vocabs['token_char']
+        V = pv.size
+
+        def cls(w):
+            return 1 if w == UNK else 2 if w == END else 0
+
+        def chars(ws):
+            return strings_to_char_tensor([ws], cv)[:, 0] if ws else None
+        shared = self.__dict__.get('_search_shared')
+        if shared is None or shared[0] != (V, str(self.device)):
+            words = [pv.idx2token(i) for i in range(V)]
+            shared = ((V, str(self.device)), torch.tensor([cls(w) for w in words], dtype=torch.uint8).to(self.device),
+                      torch.tensor(tv.token2idx(words), dtype=torch.int64).to(self.device), chars(words).to(self.device))
+            self.__dict__['_search_shared'] = shared
+        B, L = len(local_idx2token), tot - V
+        C = shared[3].shape[1]
+        flag_l = torch.zeros((B, max(L, 0)), dtype=torch.uint8)
+        tok_l = torch.full((B, max(L, 0)), tv.unk_idx, dtype=torch.int64)
+        char_l = torch.zeros((B, max(L, 0), C), dtype=torch.int64)
+        for b, local in enumerate(local_idx2token):
+            items = sorted((i, w) for i, w in local.items() if V <= i < tot)
+            for i, w in local.items():
+                if i < V and w != pv.idx2token(i):
+                    raise ValueError("copy id %d of graph %d lies inside the vocabulary (%r vs %r)" % (i, b, w, pv.idx2token(i)))
+            if items:
+                ids = [i - V for i, _ in items]
+                words = [w for _, w in items]
+                flag_l[b, ids] = torch.tensor([cls(w) for w in words], dtype=torch.uint8)
+                tok_l[b, ids] = torch.tensor(tv.token2idx(words), dtype=torch.int64)
+                char_l[b, ids] = chars(words)
+        start = (tv.token2idx(STR), strings_to_char_tensor([[STR]], cv)[0, 0])
+        dead = (tv.padding_idx, strings_to_char_tensor([[PAD]], cv)[0, 0])
+        dev = self.device
+        return {'V': V, 'C': C, 'flag_shared': shared[1], 'tok_shared': shared[2], 'char_shared': shared[3],
+                'flag_local': flag_l.to(dev) if L > 0 else None, 'tok_local': tok_l.to(dev) if L > 0 else None,
+                'char_local': char_l.to(dev) if L > 0 else None,
+                'start_tok': start[0], 'start_char': start[1].to(dev), 'dead_tok': dead[0], 'dead_char': dead[1].to(dev)}
+
+    def slot_caches(self, max_time_step, N):
+        """Preallocated self-attention caches of the fixed-slot search: per sentence-encoder and inference layer a pair of zeroed
+        [max_time_step, N, 2d] buffers in the layer's compute dtype."""
+        layers = list(self.snt_encoder.layers) + list(self.decoder.inference_core.layers)
+        return [[torch.zeros((max_time_step, N, 2 * self.embed_dim), dtype=l.self_attn.compute_dtype, device=self.device)
+                 for _ in range(2)] for l in layers]
+
+    def decode_slots(self, inp, caches, mem, t):
+        """Step t of the fixed-slot search: inp = (step_token [1,N], step_token_char [1,N,C]); caches: one [T_max,N,2d] buffer per
+        sentence-encoder layer, then per inference layer (rows [0,t) hold the prefix, row t is written); mem: everything per slot.
+        -> ll [N, V+ext] fp32."""
+        n_snt = len(self.snt_encoder.layers)
+        x = self._step_embed(inp, t)
+        for li, layer in enumerate(self.snt_encoder.layers):
+            x = layer.step_into(x, x, caches[li], t, mem['snt_ext_kv'][li], mem['graph_padding_mask'])
+        return self.decoder.step_into(mem['probe'], x, caches[n_snt:], t, mem)[0]
 
     def prepare_incremental_input(self, step_seq):
         """step_seq: one single-token list per live hypothesis (generator.py:112-117).  Token id and character row of a
@@ -196,14 +263,17 @@ class Generator(nn.Module):
                                               mem, offset, topk)
         return {'snt': snt, 'inf': inf}, results
 
-    def _decode_core(self, inp, snt_state, inf_state, mem, offset, topk):
-        """inp = (step_token [1,N], step_token_char [1,N,C]); snt_state / inf_state: per layer [t,N,2d] or None; mem: everything
-        already per hypothesis.  -> (new sentence-encoder caches, new inference caches, top-k results)."""
+    def _step_embed(self, inp, offset):
         step_token, step_token_char = inp
         pos = self.token_position(step_token, offset).to(self.compute_dtype)
         x = self.embed_scale * self.token_encoder(step_token, step_token_char) + pos
         ln = self.token_embed_layer_norm
-        x = ops.layer_norm_residual(x, None, ln.weight, ln.bias, 0.0, ln.eps)
+        return ops.layer_norm_residual(x, None, ln.weight, ln.bias, 0.0, ln.eps)
+
+    def _decode_core(self, inp, snt_state, inf_state, mem, offset, topk):
+        """inp = (step_token [1,N], step_token_char [1,N,C]); snt_state / inf_state: per layer [t,N,2d] or None; mem: everything
+        already per hypothesis.  -> (new sentence-encoder caches, new inference caches, top-k results)."""
+        x = self._step_embed(inp, offset)
         snt_caches = []
         for li, layer in enumerate(self.snt_encoder.layers):
             x, c = layer.step(x, x, None if snt_state is None else snt_state[li], mem['snt_ext_kv'][li], mem['graph_padding_mask'])

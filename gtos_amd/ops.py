@@ -1199,3 +1199,68 @@ def copy_log_likelihood(logits, div, align, cp_seq, tot_ext):
     call("gtos_copy_ll_fwd", dt(logits), T_, B, V, cp_seq.shape[0], tot, ptr(logits), V, ptr(div), ptr(align), ptr(cp_seq),
          ptr(ll), stream())
     return ll
+
+
+# ---------------------------------------------------------------------------------------------- device-resident beam search
+# (csrc/beam.hip; gtos_amd.search.beam_search_device drives them)
+def beam_topk(ll, k):
+    """ll [rows, tot] fp32 (row stride >= tot, unit column stride) -> (values [rows,k] fp32, columns [rows,k] int32), descending,
+    equal values lower column first."""
+    require_cuda(ll)
+    if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1:
+        raise _lib.GtosHipError("beam_topk: ll must be a 2-D fp32 tensor with unit column stride")
+    rows, tot = ll.shape
+    val = torch.empty((rows, k), dtype=torch.float32, device=ll.device)
+    idx = torch.empty((rows, k), dtype=torch.int32, device=ll.device)
+    call("gtos_beam_topk", rows, tot, k, ptr(ll), max(ll.stride(0), tot), ptr(val), ptr(idx), stream())
+    return val, idx
+
+
+def beam_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state,
+                 bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
+    """One advance of every beam at step t (gtos_beam_advance): updates slot_score, beam_state, bp_* row t, comp_*, active in place."""
+    B = beam_state.shape[0]
+    N = B * k
+    require_cuda(topv, topi, flag_shared, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active)
+    assert topv.shape == (N, k) and topi.shape == (N, k) and topv.dtype == torch.float32 and topi.dtype == torch.int32
+    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
+    assert flag_local is None or (flag_local.dtype == torch.uint8 and flag_local.numel() >= B * (tot - V))
+    assert slot_score.dtype == torch.float64 and slot_score.numel() == N and beam_state.shape == (B, 4)
+    assert bp_parent.shape == (max_time_step, N) and bp_token.shape == (max_time_step, N)
+    assert comp_step.shape == (B, k) and comp_parent.shape == (B, k) and comp_score.shape == (B, k) and active.numel() == 3
+    for x in (topv, topi, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
+        assert x is None or x.is_contiguous()
+    call("gtos_beam_advance", B, k, t, V, tot, min_time_step, max_time_step, ptr(topv), ptr(topi), ptr(flag_shared), ptr(flag_local),
+         ptr(slot_score), ptr(beam_state), ptr(bp_parent), ptr(bp_token), ptr(comp_step), ptr(comp_parent), ptr(comp_score),
+         ptr(active), stream())
+
+
+def beam_reorder(src, dst, t, k, bp_parent, bp_token, beam_state, active, V, tot, tok_shared, tok_local, char_shared, char_local,
+                 dead_tok, dead_char, tok_out, char_out):
+    """After the advance of step t: rows [0,t] of every cache src[i] ([T_max, N, w], contiguous) gathered by parent slot into dst[i],
+    and the next input (tok_out [N] int64, char_out [N,C] int64) of every slot (gtos_beam_reorder)."""
+    import ctypes
+    T_max, N = bp_parent.shape
+    C = char_out.shape[-1]
+    require_cuda(bp_parent, bp_token, beam_state, active, tok_shared, char_shared, dead_char, tok_out, char_out, *src, *dst)
+    row_bytes = 0
+    for a, b in zip(src, dst):
+        assert a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous()
+        assert a.shape[0] == T_max and a.shape[1] == N
+        rb = a[0, 0].numel() * a.element_size()
+        assert row_bytes in (0, rb), "beam_reorder: every cache must have the same row width"
+        row_bytes = rb
+    assert len(src) == len(dst) and (len(src) == 0 or row_bytes > 0)
+    for x in (tok_shared, char_shared, dead_char, tok_out, char_out, tok_local, char_local):
+        assert x is None or (x.dtype == torch.int64 and x.is_contiguous())
+    assert tok_out.numel() == N and char_out.numel() == N * C and dead_char.numel() == C and char_shared.shape[-1] == C
+    assert tok_shared.numel() >= V and char_shared.numel() >= V * C
+    if tot > V:
+        B = N // k
+        assert tok_local.numel() >= B * (tot - V) and char_local.numel() >= B * (tot - V) * C
+    n = len(src)
+    S = (ctypes.c_void_p * max(1, n))(*[x.data_ptr() for x in src])
+    D = (ctypes.c_void_p * max(1, n))(*[x.data_ptr() for x in dst])
+    call("gtos_beam_reorder", n, ctypes.addressof(S), ctypes.addressof(D), row_bytes or 16, N, k, t, T_max, ptr(bp_parent), ptr(bp_token),
+         ptr(beam_state), ptr(active), V, tot, ptr(tok_shared), ptr(tok_local), ptr(char_shared), ptr(char_local), C, int(dead_tok),
+         ptr(dead_char), ptr(tok_out), ptr(char_out), stream())

@@ -11,9 +11,14 @@ What differs is the machinery: hypotheses carry no tensors.  The decoder state o
 is one set of K/V-cache tensors ``[t, N, 2d]`` (gtos_amd.generator.Generator.decode_step_batched); a step returns, per beam,
 the parent index of every surviving hypothesis, and the caches are re-gathered with ONE index_select per tensor
 instead of being split into per-hypothesis slices and concatenated again.
+
+``beam_search_device`` runs the same rules with the bookkeeping on the GPU as well (csrc/beam.hip): B sentences x k fixed
+hypothesis slots, the graph memory gathered per slot once, preallocated caches reordered by a kernel, and the host reading one
+flag every ``sync_every`` steps and the back-pointer / completion tables once at the end.
 """
 import torch
 
+from . import ops
 from .vocab import END, UNK, STR
 
 
@@ -104,4 +109,105 @@ def beam_search(model, beams, memory):
             break
         idx = torch.tensor(keep, dtype=torch.int64, device=device)
         state = {k: [c.index_select(1, idx) for c in v] for k, v in state.items()}
+    return beams
+
+
+def beam_search_device(model, memory, beams, sync_every=8, stats=None):
+    """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
+    decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
+    steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
+    keep computing on the padding input and zero cache rows, their candidates are ignored.  The loop reads the device's "some
+    not-done beam has a live slot" flag every ``sync_every`` steps (steps past the end are no-ops); at the end the tables are read
+    once and the Beam objects filled as beam_search leaves them (hypotheses, completed_hypotheses in append order, steps).
+    ``stats`` (a dict, optional) receives the decoder steps launched and the host reads made."""
+    B = len(beams)
+    if not B:
+        return beams
+    k, min_t, max_t = beams[0].beam_size, beams[0].min_time_step, beams[0].max_time_step
+    for beam in beams:
+        assert (beam.beam_size, beam.min_time_step, beam.max_time_step) == (k, min_t, max_t), "beams of one search share their settings"
+        assert beam.steps == 0 and len(beam.hypotheses) == 1 and not beam.completed_hypotheses, "beam_search_device takes fresh beams"
+    n_steps, reads = 0, 0
+    if max_t <= 0:                                          # every beam is complete before the first step
+        if stats is not None:
+            stats.update(steps=0, host_reads=0)
+        return beams
+    dev = memory['probe'].device
+    N = B * k
+    graph_of = torch.arange(N, device=dev) // k
+    sel = lambda v: v.index_select(1, graph_of)
+    mem = {'graph_padding_mask': sel(memory['graph_padding_mask']), 'cp_seq': sel(memory['cp_seq']), 'probe': sel(memory['probe']),
+           'tot_ext': memory['tot_ext'], 'snt_ext_kv': [sel(v) for v in memory['snt_ext_kv']],
+           'inf_ext_kv': [sel(v) for v in memory['inf_ext_kv']], 'align_kv': sel(memory['align_kv'])}
+    local = memory['local_idx2token']
+    V = model.vocabs['predictable_token'].size
+    tot = max(int(memory['tot_ext']), V)
+    tab = model.search_tables(local, tot)
+    C = tab['C']
+    # one int32 and one fp64 arena, so that the final read is two copies
+    ints = torch.empty(3 + 4 * B + 2 * max_t * N + 2 * B * k, dtype=torch.int32, device=dev)
+    cuts = [3, 4 * B, max_t * N, max_t * N, B * k, B * k]
+    active, state, bp_parent, bp_token, comp_step, comp_parent = torch.split(ints, cuts)
+    state, bp_parent, bp_token = state.view(B, 4), bp_parent.view(max_t, N), bp_token.view(max_t, N)
+    comp_step, comp_parent = comp_step.view(B, k), comp_parent.view(B, k)
+    active.zero_()
+    active[0] = 1
+    state.zero_()
+    state[:, 2] = 1                                         # one live hypothesis (<STR>) per beam
+    bp_parent.fill_(-1)
+    bp_token.fill_(-1)
+    comp_step.zero_()
+    comp_parent.zero_()
+    dbl = torch.zeros(N + B * k, dtype=torch.float64, device=dev)
+    slot_score, comp_score = dbl[:N], dbl[N:].view(B, k)
+    caches = model.slot_caches(max_t, N)
+    tok = [torch.full((1, N), tab['dead_tok'], dtype=torch.int64, device=dev) for _ in range(2)]
+    chars = [tab['dead_char'].expand(1, N, C).contiguous() for _ in range(2)]
+    tok[0][0, ::k] = tab['start_tok']
+    chars[0][0, ::k] = tab['start_char']
+    for t in range(max_t):
+        cur, nxt = t % 2, (t + 1) % 2
+        ll = model.decode_slots((tok[cur], chars[cur]), [c[cur] for c in caches], mem, t)
+        topv, topi = ops.beam_topk(ll, k)
+        ops.beam_advance(t, k, V, tot, min_t, max_t, topv, topi, tab['flag_shared'], tab['flag_local'], slot_score, state,
+                         bp_parent, bp_token, comp_step, comp_parent, comp_score, active)
+        ops.beam_reorder([c[cur] for c in caches], [c[nxt] for c in caches], t, k, bp_parent, bp_token, state, active, V, tot,
+                         tab['tok_shared'], tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'],
+                         tab['dead_char'], tok[nxt][0], chars[nxt][0])
+        n_steps += 1
+        if (t + 1) % sync_every == 0 and t + 1 < max_t:
+            reads += 1
+            if not int(active[(t + 1) % 3].item()):
+                break
+    ints_h, dbl_h = ints.cpu(), dbl.cpu()
+    reads += 2
+    if stats is not None:
+        stats.update(steps=n_steps, host_reads=reads)
+    _, state, bp_parent, bp_token, comp_step, comp_parent = [x.tolist() for x in torch.split(ints_h, cuts)]
+    pv = model.vocabs['predictable_token']
+    return fill_beams(beams, k, state, bp_parent, bp_token, comp_step, comp_parent, dbl_h[:N].tolist(), dbl_h[N:].tolist(),
+                      lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i))
+
+
+def fill_beams(beams, k, state, bp_parent, bp_token, comp_step, comp_parent, slot_score, comp_score, token_string):
+    """The Beam objects of a fixed-slot search from its tables (flat lists): state [B*4] (steps, #completed, #live, done),
+    bp_parent / bp_token [T*N] (row t: parent slot and token id of every slot after step t), comp_step / comp_parent / comp_score
+    [B*k] (completions in append order), slot_score [N]; token_string(b, id) -> the string of an output id of graph b."""
+    N = len(beams) * k
+    for b, beam in enumerate(beams):
+        steps, ncomp, nlive = state[4 * b:4 * b + 3]
+        if steps == 0:
+            continue
+
+        def seq_of(slot, tl):
+            ids = []
+            while tl >= 0:
+                ids.append(bp_token[tl * N + slot])
+                slot = bp_parent[tl * N + slot]
+                tl -= 1
+            return [STR] + [token_string(b, i) for i in reversed(ids)]
+        beam.completed_hypotheses = [Hypothesis(seq_of(comp_parent[b * k + j], comp_step[b * k + j] - 1) + [END], comp_score[b * k + j])
+                                     for j in range(ncomp)]
+        beam.hypotheses = [Hypothesis(seq_of(b * k + j, steps - 1), slot_score[b * k + j]) for j in range(nlive)]
+        beam.steps = steps
     return beams

@@ -138,6 +138,20 @@ class TransformerLayer(nn.Module):
         xs, x = ops.split_stream(x, cd)
         row = self.self_attn.project_kv(ops.split_stream(new_kv_src, cd)[1])
         cache = row if self_cache is None else torch.cat([self_cache, row], 0)
+        return self._step_attend(xs, x, cache, ext_kv, ext_mask), cache
+
+    def step_into(self, x, new_kv_src, cache, t, ext_kv, ext_mask):
+        """step() on a preallocated self-attention cache [T_max,N,2d] whose rows [0,t) hold the prefix (the fixed-slot layout of
+        gtos_amd.search.beam_search_device): the new K/V row is written into row t and attention reads the contiguous view [:t+1].
+        Same arithmetic as step().  Returns x_out."""
+        cd = self.self_attn.compute_dtype
+        xs, x = ops.split_stream(x, cd)
+        cache[t].copy_(self.self_attn.project_kv(ops.split_stream(new_kv_src, cd)[1])[0])
+        return self._step_attend(xs, x, cache[:t + 1], ext_kv, ext_mask)
+
+    def _step_attend(self, xs, x, cache, ext_kv, ext_mask):
+        """The part of a decoding step after the new cache row exists: self-attention over `cache`, cross-attention, FFN."""
+        cd = self.self_attn.compute_dtype
         a, _ = self.self_attn.attend_cached(x, cache)
         ln = self.attn_layer_norm
         xs, x = ops.layer_norm_stream(xs, a, ln.weight, ln.bias, 0.0, ln.eps, cd)
@@ -149,7 +163,7 @@ class TransformerLayer(nn.Module):
         f = ops.linear(h, self.fc2.weight, self.fc2.bias)
         ln = self.ff_layer_norm
         xs, x = ops.layer_norm_stream(xs, f, ln.weight, ln.bias, 0.0, ln.eps, cd)
-        return ops.join_stream(xs, x), cache
+        return ops.join_stream(xs, x)
 
 
 class Transformer(nn.Module):

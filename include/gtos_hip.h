@@ -389,6 +389,35 @@ int gtos_copy_nll_bwd(int dtype, int T, int B, int V, int S, const void* logits,
 int gtos_copy_ll_fwd(int dtype, int T, int B, int V, int S, int tot_ext, const void* logits, int64_t ld_logits,
                      const void* div, const float* align, const int64_t* cp_seq, float* ll, void* stream);
 
+/* ---- Device-resident beam search (csrc/beam.hip; selection rule in csrc/beam_kernels.h), driven by
+ * gtos_amd.search.beam_search_device: generator/search.py's Beam.update / Beam.completed / search_by_batch without a host round trip
+ * per step.  B sentences x k fixed hypothesis slots, N = B*k, slot s belongs to sentence s / k.  SHAPES (-10 outside): k <= 32.
+ * _topk: per row of ll [rows, tot] fp32 (row stride ld >= tot >= k), the k largest values val [rows,k] and their columns
+ *   idx int32 [rows,k], descending, equal values lower column first (the torch.topk of generator.py:163).
+ * _advance (one workgroup per sentence, step t < max_time_step): pools the candidates (topv / topi [N,k]) of the sentence's live slots
+ *   in (slot, rank) order, scores them in fp64 (parent score slot_score[N] + ll; -inf where the token's string is <UNK>), sorts stably
+ *   descending, cuts to k - #completed; <END> candidates complete (recorded when the sentence's steps >= min_time_step, dropped
+ *   otherwise), the others become the live slots in sorted order.  Token classes (0 plain, 1 <UNK>, 2 <END>) come from flag_shared
+ *   uint8 [V] for ids < V and flag_local uint8 [B, tot-V] for the per-graph copy ids.  beam_state int32 [B,4] = steps, #completed,
+ *   #live, done; back-pointers bp_parent / bp_token int32 [max_time_step, N] (parent slot or -1, token id); completions
+ *   comp_step / comp_parent int32, comp_score fp64, [B,k] in append order.  active int32 [3] rotates the "some not-done sentence has a
+ *   live slot" flag between steps: step t runs only if active[t % 3] is set (initially {1, 0, 0}).
+ * _reorder (after _advance of step t): rows [0,t] of each of the n_caches self-attention caches src[i] ([max_time_step, N, row_bytes],
+ *   16-byte aligned, row_bytes % 16 == 0; src / dst are HOST arrays of device pointers, n_caches <= 32) gathered by parent slot into
+ *   dst[i]; dead slots get zero rows.  tok_out int64 [N] and char_out int64 [N,C] receive the next input token id and character row
+ *   of every slot from tok_shared [V] / char_shared [V,C] and tok_local [B,tot-V] / char_local [B,tot-V,C] (dead slots: dead_tok /
+ *   dead_char [C]).  After a step that did not run, only the inputs are written (all dead). */
+int gtos_beam_topk(int rows, int tot, int k, const float* ll, int64_t ld, float* val, int* idx, void* stream);
+int gtos_beam_advance(int B, int k, int t, int V, int tot, int min_time_step, int max_time_step, const float* topv,
+                      const int* topi, const uint8_t* flag_shared, const uint8_t* flag_local, double* slot_score,
+                      int* beam_state, int* bp_parent, int* bp_token, int* comp_step, int* comp_parent,
+                      double* comp_score, int* active, void* stream);
+int gtos_beam_reorder(int n_caches, void* const* src, void* const* dst, int64_t row_bytes, int N, int k, int t,
+                      int max_time_step, const int* bp_parent, const int* bp_token, const int* beam_state,
+                      const int* active, int V, int tot, const int64_t* tok_shared, const int64_t* tok_local,
+                      const int64_t* char_shared, const int64_t* char_local, int C, int64_t dead_tok,
+                      const int64_t* dead_char, int64_t* tok_out, int64_t* char_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
