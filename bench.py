@@ -4,12 +4,16 @@ Generator on synthetic 100-node AMR graphs, batch 64 per GPU, bf16 activations (
 
     python bench.py --gpus N --steps K --warmup W        (N>1: one rank per GPU; launched by torch.distributed.run, or self-launching)
 
-Prints ONE JSON line (rank 0).  Also reports
+Prints ONE JSON line (rank 0).  A plain run sets up, pre-warms, runs the W warm-up and K timed steps, writes --dump-outputs and
+prints the line: the headline and what the timed region itself recorded.  With --full the line also reports what takes runs of
+its own after the timed region:
   roofline      relation-attention forward kernel: algorithmic bytes per launch (P*2d*s + 4*n*B*d*s + n*B,
                 SURVEY.md section 8d) / average launch duration measured with HIP events on the launch stream inside the
-                timed region, against 8 TB/s HBM3E;
+                timed region, against 8 TB/s HBM3E; a dense-signature leg and a per-kernel detail pass;
   cpu_baseline  the CPU oracle (a port of the reference pinned to its golden vectors) timed on the host cores on a
-                bounded sample of the same workload (rank 0, N=1 only).
+                bounded sample of the same workload (rank 0, N=1 only);
+  node_masks / reference_masks, loader_in_loop, other_scaling (N>1), hipgraph_replay (--graph-leg): the same step in
+                another configuration.
 """
 import argparse
 import json
@@ -57,6 +61,10 @@ def parse():
     ap.add_argument("--config", default="C2")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--dense", action="store_true", help="dense relation[n,n,B,d] signature instead of the factored form")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, everything else this script measures: the roofline (dense-signature leg, per-kernel "
+                         "detail pass), the CPU baseline, the other --relation-masks mode, the loader in the loop and at N > 1 the other "
+                         "--scaling mode (about a minute more at C2); the --no-*-leg / --no-cpu-baseline / --cpu-* options tune these legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-graphs", type=int, default=4,
                     help="micro-batch of the CPU baseline (default 4 keeps the leg near 45 s; SURVEY 8d's protocol is --cpu-graphs 8 "
@@ -66,7 +74,7 @@ def parse():
     ap.add_argument("--cpu-warmup", type=int, default=1, help="untimed CPU warm-up steps (SURVEY 8d: 2)")
     ap.add_argument("--cpu-protocol", action="store_true",
                     help="SURVEY 8d's CPU protocol live in this run: --cpu-graphs 8 --cpu-warmup 2 --cpu-steps 5 --cpu-budget 600 (about five "
-                         "minutes of host time on 16 cores: more than the default run may take, hence a flag)")
+                         "minutes of host time on 16 cores: more than the --full run may take, hence a flag; implies --full)")
     ap.add_argument("--decode", action="store_true",
                     help="secondary benchmark (SURVEY 8f rank 2): beam search over the K/V-cached decoder instead of the train step")
     ap.add_argument("--beam", type=int, default=8)
@@ -99,14 +107,15 @@ def parse():
                          "(generator/encoder.py:91-92,105; the library default and, since the end of round 4, this script's: one GRU row "
                          "per path and position), 'node' = drawn per node of the prefix / suffix trie and shared by the paths through it "
                          "(opt-in, gtos_amd.encoder.set_relation_mask_sharing: layer 0 once per trie node, layer-1 input gates from "
-                         "per-node tables; the headline of rounds 2-3 and of this round's earlier records).  The other mode is measured "
-                         "right after the timed region and reported as `node_masks` / `reference_masks`")
-    ap.add_argument("--no-masks-leg", action="store_true", help="skip the leg that measures the other --relation-masks mode")
+                         "per-node tables; the headline of rounds 2-3 and of this round's earlier records).  With --full the other mode is "
+                         "measured right after the timed region and reported as `node_masks` / `reference_masks`")
+    ap.add_argument("--no-masks-leg", action="store_true", help="--full: skip the leg that measures the other --relation-masks mode")
     ap.add_argument("--graph-leg", action="store_true",
-                    help="after the timed region (N = 1): the same step replayed from a hipGraph (train.GraphedStep).  Opt-in: on ROCm "
-                         "7.2 the capture of the multi-stream C2 step crashes inside hipStreamEndCapture (C1 captures and replays)")
+                    help="after the timed region (N = 1): the same step replayed from a hipGraph (train.GraphedStep); implies --full.  Opt-in: "
+                         "on ROCm 7.2 the capture of the multi-stream C2 step crashes inside hipStreamEndCapture (C1 captures and replays)")
     ap.add_argument("--no-loader-leg", action="store_true",
-                    help="skip the loader-in-the-loop leg that follows the timed region of the default (pre-built batch) run")
+                    help="--full: skip the loader-in-the-loop leg that follows the timed region of a pre-built batch run (and, in any run, "
+                         "the allocator's size rounding that run sets for it)")
     ap.add_argument("--device-relations", action="store_true",
                     help="--fresh-batches: the loader ships the flattened graphs only (index_prep='device_all'); relation / bank / length "
                          "(gtos_amd.relbatch_hip), the relation index (gtos_amd.relindex_hip) and the tries (gtos_amd.pathtrie_hip) are built on "
@@ -131,6 +140,7 @@ def parse():
                          "then starts from the trainer state before the first step (restored untimed), so that the same arguments give "
                          "it the same inputs, and the same outputs up to rounding, in every run")
     a = ap.parse_args()
+    a.full = a.full or a.cpu_protocol or a.graph_leg       # legs of the full run
     if a.steps < 1:
         ap.error("--steps must be at least 1")
     if a.dump_outputs and (a.decode or a.fresh_batches):
@@ -638,6 +648,7 @@ def main():
         # changes size from step to step; the caching allocator then keeps growing (a cached 890 MB block cannot serve an 895 MB
         # request) until hipMalloc fails and the cache is flushed -- measured: 63 ms per step for one run, 120-140 ms for the next
         # two on the same box.  Rounding request sizes up to 1/16 of a power of two makes consecutive steps reuse their blocks.
+        # A run without --full has no loader leg but sets this too, so that its timed steps run under the allocator of a --full run.
         torch.cuda.memory._set_allocator_settings("roundup_power2_divisions:16")
     # the driver releases a finished process's device memory lazily (a 100 GB process still shows 35-40 % of the VRAM allocated a
     # second after it has gone, none three seconds later): a run started back to back with another one would otherwise begin under
@@ -796,7 +807,7 @@ def main():
             rccl_info["rccl_version"] = ".".join(str(v) for v in torch.cuda.nccl.version())
         except Exception:                     # noqa: BLE001
             pass
-        if not a.fresh_batches and B_cfg % world == 0:
+        if a.full and not a.fresh_batches and B_cfg % world == 0:
             B_other = B_cfg // world if a.scaling == "weak" else B_cfg
             b2, st2 = synth.make_config_batch(a.config, rank=rank, B=B_other)
             attach_relation_index(attach_path_trie(b2))
@@ -820,7 +831,7 @@ def main():
     # (N > 1 runs keep to the legs that cannot strand a rank inside a collective: the other scaling mode above; the mask-mode and loader
     #  legs run at N = 1 -- or everywhere with GTOS_BENCH_ALL_LEGS=1)
     all_legs = world == 1 or bool(os.environ.get("GTOS_BENCH_ALL_LEGS"))
-    if not a.no_masks_leg and cd == torch.bfloat16 and not a.fresh_batches and all_legs:
+    if a.full and not a.no_masks_leg and cd == torch.bfloat16 and not a.fresh_batches and all_legs:
         other = "path" if a.relation_masks == "node" else "node"
         set_relation_mask_sharing(model, other)
         # the other mode is another set of buffer sizes: the cache is full of blocks cut for the headline's (with three warm-up steps on
@@ -849,7 +860,7 @@ def main():
     # above is the pre-built batch SURVEY 8d prescribes; this leg says what feeding costs on top of it.
     loader_leg = None
     # (round 5: this leg runs at every N -- one loader worker process per rank, N of them on the host -- the other secondary legs at N = 1)
-    if not a.fresh_batches and not a.no_loader_leg and cd == torch.bfloat16 and not a.dense:
+    if a.full and not a.fresh_batches and not a.no_loader_leg and cd == torch.bfloat16 and not a.dense:
         try:
             # the cache is full of blocks cut for ONE batch's sizes; the loader's batches all differ by a percent.  At C2 that costs
             # nothing, at C5 (95 GB allocated, 230+ GB cached) the first varying-size steps overflow the device and every step pays a
@@ -944,7 +955,7 @@ def main():
                   "graph_encoder_fwd_ms": span(prof, "graph_encoder_fwd")[0],
                   "note": "HIP-event spans on the main stream inside the timed region, per step"}
     roofline = None
-    if rank == 0:
+    if rank == 0 and a.full:
         # N > 1: no detail pass (its extra training steps would issue collectives the other ranks do not join)
         roofline = build_roofline(a, cfg, stats, model, trainer, batch, prof, dev, cd,
                                   detail=(world == 1 and not os.environ.get("GTOS_BENCH_NO_DETAIL")))
@@ -961,7 +972,7 @@ def main():
         metric = ("graphs/sec training step (100-node AMR, batch 64)" if a.config in ("C2", "C4") else
                   "graphs/sec training step (%s: %d-node %s graphs, batch %d)" % (a.config, cfg["N"], cfg["kind"], B))
         out = {"metric": metric, "value": world * B * a.steps / elapsed,
-               "unit": "graphs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+               "unit": "graphs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "full": a.full,
                "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True, "scaling": a.scaling,
                "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
                "config": {"workload": "%s: %s %dx%d-node synthetic %s %s, %d-layer d=%d %d-head, "
@@ -980,7 +991,7 @@ def main():
                                            "the reference's dropout semantics (the library default): masks per (path, position), one GRU row "
                                            "each, on the packed-path kernels (gtos_amd.gru.PackedPathGRUFn: no host read, input gradients inside "
                                            "the backward step launches, grouped weight gradients); the trie-shared masks of rounds 2-3 (an opt-in, "
-                                           "a different regulariser) are measured in the same run: see node_masks"),
+                                           "a different regulariser) are measured in a --full run: see node_masks"),
                           "allreduce_exposed_ms_per_step": round(1e3 * max(r[1] for r in per_rank) / a.steps, 3),
                           "per_rank_ms_per_step": [round(1e3 * r[0] / a.steps, 3) for r in per_rank],
                           "per_rank_allreduce_exposed_ms_per_step": [round(1e3 * r[1] / a.steps, 3) for r in per_rank],
@@ -991,7 +1002,7 @@ def main():
                "roofline": roofline, "components": components, "loader_in_loop": loader_leg, "hipgraph_replay": graph_leg,
                ("reference_masks" if a.relation_masks == "node" else "node_masks"): masks_leg,
                "other_scaling": other_scaling, "collectives": rccl_info}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.config, a.cpu_graphs, a.cpu_steps, a.cpu_budget, a.cpu_warmup)
             out["cpu_baseline"]["leg"] = (
                 "SURVEY 8d protocol, live in this run (8 graphs, 2 warm-up + 5 timed steps)" if a.cpu_graphs >= 8 and a.cpu_steps >= 5 else

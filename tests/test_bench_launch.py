@@ -61,6 +61,16 @@ def test_bench_defaults_are_the_library_defaults(monkeypatch):
     assert a.gpus == 1 and a.config == "C2" and not a.graph_leg and not a.fresh_batches
 
 
+def test_plain_run_leaves_the_secondary_legs_to_full(monkeypatch):
+    """`python bench.py` runs what its headline needs; --full adds the legs after the timed region, and the options that only add to
+    those legs imply it."""
+    bench = _bench_module("bench_mod5")
+    for argv, full in (([], False), (["--no-cpu-baseline", "--no-masks-leg"], False), (["--full"], True), (["--cpu-protocol"], True),
+                       (["--config", "C1", "--graph-leg"], True)):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        assert bench.parse().full is full, argv
+
+
 def _bench_module(name):
     import importlib.util
     spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "bench.py"))

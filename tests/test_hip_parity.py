@@ -1415,14 +1415,14 @@ def test_bench_two_ranks_on_one_gpu_functional():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(GTOS_ONE_DEVICE="1", GTOS_DIST_BACKEND="gloo", GTOS_BENCH_ALL_LEGS="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "C1", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--prewarm-seconds", "1"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--prewarm-seconds", "1"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 2 * d["config"]["B_per_gpu"] and d["scaling"] == "weak"
     assert d["value"] > 0 and np.isfinite(d["config"]["loss_last"])
     assert "allreduce_exposed_ms_per_step" in d["config"]
-    # round 4: one command, one line, both scaling modes + what the collective layer saw + the secondary legs
+    # --full: one command, one line, both scaling modes + what the collective layer saw + the secondary legs
     assert d["collectives"]["ranks_seen_by_allreduce"] == 2 and d["collectives"]["backend"] == "gloo"
     o = d["other_scaling"]
     assert o["scaling"] == "strong" and o["global_batch"] == d["config"]["B_per_gpu"] and o["value"] > 0
@@ -1462,6 +1462,15 @@ def test_bench_dump_outputs_repeat_whatever_the_warmup(tmp_path):
         assert rel < {"loss": 1e-5, "params": 1e-6}.get(k, 1e-4), (k, rel)
         total += v.nbytes
     assert runs[0]["adam_m"].any() and runs[0]["adam_v"].any() and total <= 64 * 2 ** 20
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """Without --full a run sets up, warms up, times its steps and prints the line: no leg after the timed region, while the spans
+    the timed region records itself are still reported."""
+    d = _bench_line(["--config", "C1", "--steps", "3", "--warmup", "1", "--prewarm-seconds", "1"])
+    assert d["full"] is False and d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and np.isfinite(d["config"]["loss_last"])
+    assert "cpu_baseline" not in d and d["roofline"] is None and d["node_masks"] is None and d["loader_in_loop"] is None
+    assert d["other_scaling"] is None and d["hipgraph_replay"] is None and d["components"]["relation_encoder_fwd_ms"] > 0
 
 
 def test_bench_strong_scaling_two_ranks_on_one_gpu_functional():

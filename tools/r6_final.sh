@@ -9,7 +9,7 @@ R=$PWD
 ( time timeout 1500 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider -s > $O/gpu_tests.log 2>&1 ) 2> $O/gpu_tests.time
 tail -4 $O/gpu_tests.log | cut -c1-300; grep real $O/gpu_tests.time; grep -a "MEASURED\|bf16 vs golden\|C2 full\|C2 B=64" $O/gpu_tests.log | cut -c1-300 > $O/measured.txt; wc -l $O/measured.txt
 timeout 300 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -2 $O/smoke.log | cut -c1-400
-( time timeout 600 python bench.py > $O/bench_c2_n1.json 2> $O/bench_c2_n1.err ) 2> $O/bench_c2_n1.time; python - <<P
+( time timeout 600 python bench.py --full > $O/bench_c2_n1.json 2> $O/bench_c2_n1.err ) 2> $O/bench_c2_n1.time; python - <<P
 import json
 try:
     d=json.loads(open("$O/bench_c2_n1.json").read().strip().splitlines()[-1]); print("bench", round(d["value"],1), round(d["ms_per_step"],2), d["components"]); r=d["roofline"]; print(r["frac"], r["in_step"]["frac"], r["in_step"].get("alone"), r["step_ceiling_ms"], r["step_frac"], d["cpu_baseline"]["value"], (d.get("node_masks") or d.get("reference_masks"))["ms_per_step"], d["loader_in_loop"]["ms_per_step"], d["config"]["device_memory"])
@@ -20,7 +20,7 @@ grep real $O/bench_c2_n1.time
 timeout 400 python bench.py --decode > $O/decode_c2.json 2> $O/decode_c2.err; tail -c 600 $O/decode_c2.json
 for c in C1 C3 C5; do
   extra=""; [ $c = C1 ] && extra="--graph-leg"
-  GTOS_BENCH_NO_DETAIL=1 timeout 500 python bench.py --config $c --steps 8 --warmup 3 --no-cpu-baseline --prewarm-seconds 8 $extra > $O/bench_$c.json 2> $O/bench_$c.err
+  GTOS_BENCH_NO_DETAIL=1 timeout 500 python bench.py --full --config $c --steps 8 --warmup 3 --no-cpu-baseline --prewarm-seconds 8 $extra > $O/bench_$c.json 2> $O/bench_$c.err
   python -c "
 import json
 try:
