@@ -8,7 +8,9 @@ exact same function as the reference's ``relation.index_select(0, idx).view(n,n,
 (decode_step_batched): the reference re-projects the whole prefix in every layer at every step.  ``decode_step`` keeps the
 reference's signature (generator.py:119) for callers that bring their own search loop.
 """
+import ctypes
 import math
+import numbers
 
 import torch
 from torch import nn
@@ -19,8 +21,23 @@ from .encoder import TokenEncoder, RelationEncoder
 from .decoder import DecodeLayer
 from .transformer import Transformer, SinusoidalPositionalEmbedding, SelfAttentionMask
 from .graph_transformer import GraphTransformer, set_compute_dtype
-from .search import Beam, beam_search, beam_search_device
+from .search import Beam, beam_search, beam_search_device, sample_device
 from .vocab import PAD, UNK, STR, END, lists_to_tensor, strings_to_char_tensor
+
+
+def check_sampling(samples, temperature, top_k, top_p, seed):
+    """The argument checks of Generator.work(search="sample"): ValueError on anything gtos_sample_step would refuse."""
+    if isinstance(samples, bool) or not isinstance(samples, numbers.Integral) or samples < 1:
+        raise ValueError("beam_size (samples per graph) must be an integer >= 1, got %r" % (samples,))
+    if (isinstance(temperature, bool) or not isinstance(temperature, numbers.Real)
+            or not (0 < ctypes.c_float(temperature).value < math.inf)):           # the kernel takes it as fp32
+        raise ValueError("temperature must be a number > 0, finite in fp32, got %r" % (temperature,))
+    if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or not 0 <= top_k <= 32:
+        raise ValueError("top_k must be an integer in [0, 32] (0 = off), got %r" % (top_k,))
+    if isinstance(top_p, bool) or not isinstance(top_p, numbers.Real) or not (0 < ctypes.c_float(top_p).value and top_p <= 1):
+        raise ValueError("top_p must lie in (0, 1] and be > 0 in fp32, got %r" % (top_p,))
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, numbers.Integral)):
+        raise ValueError("seed must be an integer or None, got %r" % (seed,))
 
 
 class Generator(nn.Module):
@@ -138,12 +155,21 @@ class Generator(nn.Module):
         return out
 
     # ------------------------------------------------------------------------------------------------ inference
-    def work(self, data, beam_size, max_time_step, min_time_step=1, search="host"):
+    def work(self, data, beam_size, max_time_step, min_time_step=1, search="host", *, temperature=1.0, top_k=0, top_p=1.0,
+             seed=None):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
-        step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU)."""
-        if search not in ("host", "device"):
-            raise ValueError("search must be 'host' or 'device', got %r" % (search,))
+        step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
+        "sample": gtos_amd.search.sample_device, ``beam_size`` independent samples per graph drawn with ``temperature``, ``top_k``
+        (0 = off, at most 32) and ``top_p`` from ``seed`` (None: ops.next_seed()); these four keywords belong to "sample" only."""
+        if search not in ("host", "device", "sample"):
+            raise ValueError("search must be 'host', 'device' or 'sample', got %r" % (search,))
+        if search == "sample":
+            check_sampling(beam_size, temperature, top_k, top_p, seed)
+            if seed is None:
+                seed = ops.next_seed()
+        elif (temperature, top_k, top_p, seed) != (1.0, 0, 1.0, None):
+            raise ValueError("temperature, top_k, top_p and seed apply to search='sample' only")
         with torch.no_grad():
             concept_repr, concept_mask, probe = self.encode_step(data, train=False)
             concept_repr = concept_repr.contiguous()
@@ -162,6 +188,8 @@ class Generator(nn.Module):
             beams = [Beam(beam_size, min_time_step, max_time_step) for _ in range(concept_repr.size(1))]
             if search == "device":
                 beam_search_device(self, memory, beams)
+            elif search == "sample":
+                sample_device(self, memory, beams, temperature, top_k, top_p, seed)
             else:
                 beam_search(self, beams, memory)
         return beams
@@ -210,12 +238,25 @@ class Generator(nn.Module):
                 'char_local': char_l.to(dev) if L > 0 else None,
                 'start_tok': start[0], 'start_char': start[1].to(dev), 'dead_tok': dead[0], 'dead_char': dead[1].to(dev)}
 
-    def slot_caches(self, max_time_step, N):
-        """Preallocated self-attention caches of the fixed-slot search: per sentence-encoder and inference layer a pair of zeroed
-        [max_time_step, N, 2d] buffers in the layer's compute dtype."""
+    def sample_tables(self, local_idx2token, tot):
+        """For gtos_amd.search.sample_device, next to search_tables: owned uint8 [B, tot-V], 1 where copy id V + i belongs to graph
+        b (is in its local_idx2token); None when tot == V."""
+        V = self.vocabs['predictable_token'].size
+        if tot <= V:
+            return None
+        owned = torch.zeros((len(local_idx2token), tot - V), dtype=torch.uint8)
+        for b, local in enumerate(local_idx2token):
+            ids = [i - V for i in local if V <= i < tot]
+            if ids:
+                owned[b, ids] = 1
+        return owned.to(self.device)
+
+    def slot_caches(self, max_time_step, N, copies=2):
+        """Preallocated self-attention caches of the fixed-slot search: per sentence-encoder and inference layer ``copies`` zeroed
+        [max_time_step, N, 2d] buffers in the layer's compute dtype (a pair for the beam search's reorder, one for sampling)."""
         layers = list(self.snt_encoder.layers) + list(self.decoder.inference_core.layers)
         return [[torch.zeros((max_time_step, N, 2 * self.embed_dim), dtype=l.self_attn.compute_dtype, device=self.device)
-                 for _ in range(2)] for l in layers]
+                 for _ in range(copies)] for l in layers]
 
     def decode_slots(self, inp, caches, mem, t):
         """Step t of the fixed-slot search: inp = (step_token [1,N], step_token_char [1,N,C]); caches: one [T_max,N,2d] buffer per

@@ -1264,3 +1264,35 @@ def beam_reorder(src, dst, t, k, bp_parent, bp_token, beam_state, active, V, tot
     call("gtos_beam_reorder", n, ctypes.addressof(S), ctypes.addressof(D), row_bytes or 16, N, k, t, T_max, ptr(bp_parent), ptr(bp_token),
          ptr(beam_state), ptr(active), V, tot, ptr(tok_shared), ptr(tok_local), ptr(char_shared), ptr(char_local), C, int(dead_tok),
          ptr(dead_char), ptr(tok_out), ptr(char_out), stream())
+
+
+# ---------------------------------------------------------------------------------------------- device-resident sampling decode
+# (csrc/sample.hip; gtos_amd.search.sample_device drives it)
+def sample_step(t, k, V, tot, min_time_step, max_time_step, temperature, top_k, top_p, seed, ll, flag_shared, flag_local, owned_local,
+                score, slot_state, tokens, active, tok_shared, tok_local, char_shared, char_local, dead_tok, dead_char, tok_out,
+                char_out):
+    """One sampling step of every slot at step t (gtos_sample_step): draws from ll [N, tot] fp32, updates score, slot_state, row t of
+    tokens and active in place, and writes the next input (tok_out [N] int64, char_out [N,C] int64)."""
+    require_cuda(ll, flag_shared, score, slot_state, tokens, active, tok_shared, char_shared, dead_char, tok_out, char_out)
+    N = slot_state.shape[0]
+    C = char_out.shape[-1]
+    if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1 or ll.shape != (N, tot):
+        raise _lib.GtosHipError("sample_step: ll must be an [N, tot] fp32 tensor with unit column stride")
+    assert slot_state.shape == (N, 3) and slot_state.dtype == torch.int32 and score.dtype == torch.float64 and score.numel() == N
+    assert tokens.shape == (max_time_step, N) and tokens.dtype == torch.int32 and active.numel() == 3 and active.dtype == torch.int32
+    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
+    if tot > V:
+        B = N // k
+        for x in (flag_local, owned_local):
+            assert x is not None and x.dtype == torch.uint8 and x.numel() >= B * (tot - V)
+        assert tok_local.numel() >= B * (tot - V) and char_local.numel() >= B * (tot - V) * C
+    for x in (tok_shared, char_shared, dead_char, tok_out, char_out, tok_local, char_local):
+        assert x is None or (x.dtype == torch.int64 and x.is_contiguous())
+    assert tok_out.numel() == N and char_out.numel() == N * C and dead_char.numel() == C and char_shared.shape[-1] == C
+    assert tok_shared.numel() >= V and char_shared.numel() >= V * C
+    for x in (flag_shared, flag_local, owned_local, score, slot_state, tokens, active):
+        assert x is None or x.is_contiguous()
+    call("gtos_sample_step", N, k, t, V, tot, min_time_step, max_time_step, float(temperature), top_k, float(top_p),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ll), max(ll.stride(0), tot), ptr(flag_shared), ptr(flag_local), ptr(owned_local),
+         ptr(score), ptr(slot_state), ptr(tokens), ptr(active), ptr(tok_shared), ptr(tok_local), ptr(char_shared), ptr(char_local), C,
+         int(dead_tok), ptr(dead_char), ptr(tok_out), ptr(char_out), stream())

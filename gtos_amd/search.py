@@ -15,6 +15,9 @@ instead of being split into per-hypothesis slices and concatenated again.
 ``beam_search_device`` runs the same rules with the bookkeeping on the GPU as well (csrc/beam.hip): B sentences x k fixed
 hypothesis slots, the graph memory gathered per slot once, preallocated caches reordered by a kernel, and the host reading one
 flag every ``sync_every`` steps and the back-pointer / completion tables once at the end.
+
+``sample_device`` decodes by sampling instead (csrc/sample.hip): the same fixed slots, one independent sample per slot with
+temperature / top-k / top-p, and Beam objects filled the same way.
 """
 import torch
 
@@ -134,11 +137,7 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None):
         return beams
     dev = memory['probe'].device
     N = B * k
-    graph_of = torch.arange(N, device=dev) // k
-    sel = lambda v: v.index_select(1, graph_of)
-    mem = {'graph_padding_mask': sel(memory['graph_padding_mask']), 'cp_seq': sel(memory['cp_seq']), 'probe': sel(memory['probe']),
-           'tot_ext': memory['tot_ext'], 'snt_ext_kv': [sel(v) for v in memory['snt_ext_kv']],
-           'inf_ext_kv': [sel(v) for v in memory['inf_ext_kv']], 'align_kv': sel(memory['align_kv'])}
+    mem = slot_memory(memory, B, k)
     local = memory['local_idx2token']
     V = model.vocabs['predictable_token'].size
     tot = max(int(memory['tot_ext']), V)
@@ -189,6 +188,15 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None):
                       lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i))
 
 
+def slot_memory(memory, B, k):
+    """The graph memory of Generator.work (B graphs) gathered once per fixed slot: slot s reads graph s // k."""
+    graph_of = torch.arange(B * k, device=memory['probe'].device) // k
+    sel = lambda v: v.index_select(1, graph_of)
+    return {'graph_padding_mask': sel(memory['graph_padding_mask']), 'cp_seq': sel(memory['cp_seq']), 'probe': sel(memory['probe']),
+            'tot_ext': memory['tot_ext'], 'snt_ext_kv': [sel(v) for v in memory['snt_ext_kv']],
+            'inf_ext_kv': [sel(v) for v in memory['inf_ext_kv']], 'align_kv': sel(memory['align_kv'])}
+
+
 def fill_beams(beams, k, state, bp_parent, bp_token, comp_step, comp_parent, slot_score, comp_score, token_string):
     """The Beam objects of a fixed-slot search from its tables (flat lists): state [B*4] (steps, #completed, #live, done),
     bp_parent / bp_token [T*N] (row t: parent slot and token id of every slot after step t), comp_step / comp_parent / comp_score
@@ -209,5 +217,102 @@ def fill_beams(beams, k, state, bp_parent, bp_token, comp_step, comp_parent, slo
         beam.completed_hypotheses = [Hypothesis(seq_of(comp_parent[b * k + j], comp_step[b * k + j] - 1) + [END], comp_score[b * k + j])
                                      for j in range(ncomp)]
         beam.hypotheses = [Hypothesis(seq_of(b * k + j, steps - 1), slot_score[b * k + j]) for j in range(nlive)]
+        beam.steps = steps
+    return beams
+
+
+def sample_bits(seed, graph, sample, t, cols):
+    """The 64-bit counter hash of csrc/sample_kernels.h for the columns ``cols`` of one (seed, graph, sample, step) row, as numpy
+    uint64: draw i of a splitmix64 stream seeded with s is ``synth.SplitMix64(s).u64(i + 1)[i]``; the row's key is three chained
+    draws (graph, sample, step) from the seed, and column c is draw c of the stream seeded with that key."""
+    import numpy as np
+    from .synth import SplitMix64
+    key = int(seed) & 0xFFFFFFFFFFFFFFFF
+    for w in (graph, sample, t):
+        key = int(SplitMix64(key).u64(int(w) + 1)[int(w)])
+    cols = np.asarray(cols, dtype=np.int64)
+    return SplitMix64(key).u64(int(cols.max()) + 1 if cols.size else 0)[cols]
+
+
+def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_every=8, stats=None):
+    """Sampling decode on the device (csrc/sample.hip), the counterpart of beam_search_device with the same ``memory``: every graph
+    gets ``beam_size`` independent samples in fixed slots (slot s is sample s % k of graph s // k), each drawing its next token by the
+    rule of csrc/sample_kernels.h (temperature, top_k, top_p; <UNK>, other graphs' copy ids and <END> before min_time_step are never
+    drawn) from a counter hash of (seed, graph, sample, step, column).  A sample never changes parent, so each layer keeps ONE
+    [max_time_step, N, 2d] cache and nothing is reordered.  The host reads the continue flag every ``sync_every`` steps and the
+    tables once at the end.  Returns the beams filled like a beam search's: completed_hypotheses (ended by <END>) by completion step,
+    then sample index; hypotheses (unfinished) in sample order; score = the fp64 sum of the model's ll of the drawn tokens.
+    ``stats`` (a dict, optional) receives the decoder steps launched and the host reads made."""
+    B = len(beams)
+    if not B:
+        return beams
+    k, min_t, max_t = beams[0].beam_size, beams[0].min_time_step, beams[0].max_time_step
+    for beam in beams:
+        assert (beam.beam_size, beam.min_time_step, beam.max_time_step) == (k, min_t, max_t), "beams of one search share their settings"
+        assert beam.steps == 0 and len(beam.hypotheses) == 1 and not beam.completed_hypotheses, "sample_device takes fresh beams"
+    n_steps, reads = 0, 0
+    if max_t <= 0:
+        if stats is not None:
+            stats.update(steps=0, host_reads=0)
+        return beams
+    dev = memory['probe'].device
+    N = B * k
+    mem = slot_memory(memory, B, k)
+    local = memory['local_idx2token']
+    V = model.vocabs['predictable_token'].size
+    tot = max(int(memory['tot_ext']), V)
+    tab = model.search_tables(local, tot)
+    owned = model.sample_tables(local, tot)
+    C = tab['C']
+    ints = torch.empty(3 + 3 * N + max_t * N, dtype=torch.int32, device=dev)
+    cuts = [3, 3 * N, max_t * N]
+    active, state, tokens = torch.split(ints, cuts)
+    state, tokens = state.view(N, 3), tokens.view(max_t, N)
+    active.zero_()
+    active[0] = 1
+    state.zero_()
+    state[:, 1] = -1                                        # no completion yet
+    tokens.fill_(-1)
+    score = torch.zeros(N, dtype=torch.float64, device=dev)
+    caches = [c[0] for c in model.slot_caches(max_t, N, copies=1)]
+    tok = [torch.full((1, N), tab['start_tok'], dtype=torch.int64, device=dev) for _ in range(2)]
+    chars = [tab['start_char'].expand(1, N, C).contiguous() for _ in range(2)]
+    for t in range(max_t):
+        cur, nxt = t % 2, (t + 1) % 2
+        ll = model.decode_slots((tok[cur], chars[cur]), caches, mem, t)
+        ops.sample_step(t, k, V, tot, min_t, max_t, temperature, top_k, top_p, seed, ll, tab['flag_shared'], tab['flag_local'], owned,
+                        score, state, tokens, active, tab['tok_shared'], tab['tok_local'], tab['char_shared'], tab['char_local'],
+                        tab['dead_tok'], tab['dead_char'], tok[nxt][0], chars[nxt][0])
+        n_steps += 1
+        if (t + 1) % sync_every == 0 and t + 1 < max_t:
+            reads += 1
+            if not int(active[(t + 1) % 3].item()):
+                break
+    ints_h, score_h = ints.cpu(), score.cpu()
+    reads += 2
+    if stats is not None:
+        stats.update(steps=n_steps, host_reads=reads)
+    _, state, tokens = [x.tolist() for x in torch.split(ints_h, cuts)]
+    pv = model.vocabs['predictable_token']
+    return fill_samples(beams, k, state, tokens, score_h.tolist(), lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i))
+
+
+def fill_samples(beams, k, state, tokens, score, token_string):
+    """The Beam objects of a sampling decode from its tables (flat lists): state [N*3] (steps, completion step or -1, dead), tokens
+    [T*N] (row t: the token id every slot drew at step t, or -1), score [N]; token_string(b, id) -> the string of an output id of
+    graph b.  A graph's steps are the most any of its slots took part in."""
+    N = len(beams) * k
+    for b, beam in enumerate(beams):
+        slots = range(b * k, b * k + k)
+        steps = max(state[3 * s] for s in slots)
+        if steps == 0:
+            continue
+
+        def seq_of(s, n):
+            return [STR] + [token_string(b, tokens[u * N + s]) for u in range(n)]
+        done = sorted((state[3 * s + 1], s) for s in slots if state[3 * s + 1] >= 0)
+        beam.completed_hypotheses = [Hypothesis(seq_of(s, e) + [END], score[s]) for e, s in done]
+        # unfinished: every step drew a token, except the step a slot stopped in for want of an allowed column
+        beam.hypotheses = [Hypothesis(seq_of(s, state[3 * s] - state[3 * s + 2]), score[s]) for s in slots if state[3 * s + 1] < 0]
         beam.steps = steps
     return beams

@@ -418,6 +418,26 @@ int gtos_beam_reorder(int n_caches, void* const* src, void* const* dst, int64_t 
                       const int64_t* char_shared, const int64_t* char_local, int C, int64_t dead_tok,
                       const int64_t* dead_char, int64_t* tok_out, int64_t* char_out, void* stream);
 
+/* ---- Device-resident sampling decode (csrc/sample.hip; selection rule in csrc/sample_kernels.h), driven by
+ * gtos_amd.search.sample_device: B graphs x k independent samples, N = B*k, slot s is sample s % k of graph s / k.  One workgroup per
+ * slot row of ll [N, tot] fp32 (row stride ld >= tot).  SHAPES (-10 outside): N % k == 0, 0 <= t < max_time_step, V <= tot,
+ * C >= 1, 0 <= top_k <= 32 (0 = off), 0 < temperature < inf, 0 < top_p <= 1.
+ * _step: a live slot draws one column from its row: the allowed columns (finite ll; not <UNK>; copy ids the slot's graph owns,
+ *   owned_local uint8 [B, tot-V]; <END> only once t >= min_time_step), cut to the top_k best (ll descending, lower column first),
+ *   then to the smallest ll threshold whose set holds a top_p share of sum exp((ll - max) / temperature) (fp64; ties kept), and
+ *   picked by Gumbel-max, argmax ll / temperature + g with g from a splitmix64 hash of (seed, s / k, s % k, t, column).  It adds
+ *   ll[winner] to score fp64 [N], writes the winner to row t of tokens int32 [max_time_step, N] and updates slot_state int32 [N,3] =
+ *   steps, completion step (<END>) or -1, dead; a row with nothing allowed stops its slot unfinished.  Token classes as in _advance.
+ *   active int32 [3] rotates like _advance's: step t runs only if active[t % 3] is set.  Every slot's next input goes to tok_out
+ *   int64 [N] / char_out int64 [N,C] from the tables of _reorder (dead or finished slots: dead_tok / dead_char).  There is no cache
+ *   reorder: a sample's parent is itself. */
+int gtos_sample_step(int N, int k, int t, int V, int tot, int min_time_step, int max_time_step, float temperature, int top_k,
+                     float top_p, uint64_t seed, const float* ll, int64_t ld, const uint8_t* flag_shared,
+                     const uint8_t* flag_local, const uint8_t* owned_local, double* score, int* slot_state, int* tokens,
+                     int* active, const int64_t* tok_shared, const int64_t* tok_local, const int64_t* char_shared,
+                     const int64_t* char_local, int C, int64_t dead_tok, const int64_t* dead_char, int64_t* tok_out,
+                     int64_t* char_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
