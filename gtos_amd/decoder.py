@@ -2,7 +2,8 @@
 
 The decoder's self- and cross-attention, LayerNorms, FFN and vocabulary projections run on the HIP kernels, and so does
 the copy/generate mixture: one fused kernel evaluates the NLL of the target without materialising the [T,B,V+copies]
-distribution (csrc/copy_nll.hip); inference gets the full log-likelihood row from a second kernel.
+distribution (csrc/copy_nll.hip); inference gets the full log-likelihood row from a second kernel.  With label_smoothing = eps > 0
+the training loss is the reference's label_smoothed_nll_loss on that row, again without the row (csrc/copy_ls.hip).
 """
 import torch
 from torch import nn
@@ -21,9 +22,19 @@ def _padded_linear(x, lin):
     return ops.linear(x, w, lin.bias)
 
 
+def set_label_smoothing(module, eps):
+    """Label smoothing eps (the reference's label_smoothed_nll_loss) for every TokenGenerator inside ``module``; returns ``module``."""
+    eps = ops.check_label_smoothing(eps)
+    for m in module.modules():
+        if isinstance(m, TokenGenerator):
+            m.label_smoothing = eps
+    return module
+
+
 class TokenGenerator(nn.Module):
-    def __init__(self, vocabs, embed_dim, token_size, dropout):
+    def __init__(self, vocabs, embed_dim, token_size, dropout, label_smoothing=0.0):
         super().__init__()
+        self.label_smoothing = ops.check_label_smoothing(label_smoothing)     # a plain attribute: state dicts are unchanged
         self.alignment_layer = MultiheadAttention(embed_dim, 1, dropout, weights_dropout=False)
         self.alignment_layer_norm = nn.LayerNorm(embed_dim)
         self.transfer = nn.Linear(embed_dim, token_size)
@@ -61,14 +72,16 @@ class TokenGenerator(nn.Module):
                 tot_ext = 1 + int(copy_seq.max().item())
             return ops.copy_log_likelihood(logits, div, alignment_weight, copy_seq, tot_ext)
         pad = self.vocabs['predictable_token'].padding_idx
-        return ops.copy_nll(logits, div, alignment_weight, copy_seq, target, pad).sum(0)
+        return ops.copy_nll(logits, div, alignment_weight, copy_seq, target, pad, self.label_smoothing).sum(0)
 
 
 class DecodeLayer(nn.Module):
-    def __init__(self, vocabs, inference_layers, embed_dim, ff_embed_dim, num_heads, token_size, rel_size, dropout):
+    def __init__(self, vocabs, inference_layers, embed_dim, ff_embed_dim, num_heads, token_size, rel_size, dropout,
+                 label_smoothing=0.0):
         super().__init__()
+        label_smoothing = ops.check_label_smoothing(label_smoothing)
         self.inference_core = Transformer(inference_layers, embed_dim, ff_embed_dim, num_heads, dropout, with_external=True)
-        self.token_generator = TokenGenerator(vocabs, embed_dim, token_size, dropout)
+        self.token_generator = TokenGenerator(vocabs, embed_dim, token_size, dropout, label_smoothing)
         self.dropout, self.vocabs = dropout, vocabs
 
     def forward(self, probe, graph_state, snt_state, graph_padding_mask, snt_padding_mask, attn_mask,

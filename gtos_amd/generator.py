@@ -44,8 +44,9 @@ class Generator(nn.Module):
     def __init__(self, vocabs, word_char_dim, word_dim, concept_char_dim, concept_dim, cnn_filters, char2word_dim,
                  char2concept_dim, rel_dim, rnn_hidden_size, rnn_num_layers, embed_dim, ff_embed_dim, num_heads,
                  dropout, snt_layers, graph_layers, inference_layers, pretrained_file, device, depth_size=32,
-                 factored_relation=True):
+                 factored_relation=True, label_smoothing=0.0):
         super().__init__()
+        label_smoothing = ops.check_label_smoothing(label_smoothing)
         self.vocabs = vocabs
         self.concept_encoder = TokenEncoder(vocabs['concept'], vocabs['concept_char'], concept_char_dim, concept_dim,
                                             embed_dim, cnn_filters, char2concept_dim, dropout, pretrained_file)
@@ -62,7 +63,8 @@ class Generator(nn.Module):
         self.token_embed_layer_norm = nn.LayerNorm(embed_dim)
         self.concept_embed_layer_norm = nn.LayerNorm(embed_dim)
         self.self_attn_mask = SelfAttentionMask(device)
-        self.decoder = DecodeLayer(vocabs, inference_layers, embed_dim, ff_embed_dim, num_heads, concept_dim, rel_dim, dropout)
+        self.decoder = DecodeLayer(vocabs, inference_layers, embed_dim, ff_embed_dim, num_heads, concept_dim, rel_dim, dropout,
+                                   label_smoothing)
         self.dropout = dropout
         self.probe_generator = nn.Linear(embed_dim, embed_dim)
         self.device = device

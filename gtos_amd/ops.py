@@ -1183,8 +1183,65 @@ class CopyNllFn(torch.autograd.Function):
         return d_logits, d_div, d_align, None, None, None
 
 
-def copy_nll(logits, div, align, cp_seq, target, pad_idx):
-    return CopyNllFn.apply(logits, div, align, cp_seq, target, pad_idx)
+def ls_workspace_words(B, S, V):
+    """int32 words of the label-smoothing workspace (the Layout of csrc/copy_ls_kernels.h)."""
+    return 4 + 3 * B + 4 * B * S + B * ((V + 31) // 32)
+
+
+class CopyNllLsFn(torch.autograd.Function):
+    """The label-smoothed generate/copy loss of the reference (label_smoothed_nll_loss on TokenGenerator's ll row):
+    loss[t,b] = (1 - eps) * -ll[target] + eps / C * -sum_{k<C} ll[k], 0 at padded targets, C = max(V, 1 + max(cp_seq)).  One
+    launch builds the batch's copy-id groups and C on the device, one forward and one backward launch; no [T,B,C] row."""
+
+    @staticmethod
+    def forward(ctx, logits, div, align, cp_seq, target, pad_idx, eps):
+        require_cuda(logits, div, align, cp_seq, target)
+        T_, B, V = logits.shape
+        S = cp_seq.shape[0]
+        logits, div = logits.contiguous(), div.contiguous()
+        align = align.float().contiguous()
+        cp_seq, target = cp_seq.contiguous(), target.contiguous()
+        words = ls_workspace_words(B, S, V)
+        ws = torch.empty(words, dtype=torch.int32, device=logits.device)
+        call("gtos_copy_nll_ls_prep", B, S, V, ptr(cp_seq), ptr(ws), words, stream())
+        loss = torch.empty((T_, B), dtype=torch.float32, device=logits.device)
+        lse = torch.empty_like(loss)
+        sums = torch.empty((T_, B, 2), dtype=torch.float32, device=logits.device)
+        call("gtos_copy_nll_ls_fwd", dt(logits), T_, B, V, S, ptr(logits), V, ptr(div), ptr(align), ptr(target), int(pad_idx),
+             float(eps), ptr(ws), words, ptr(loss), ptr(lse), ptr(sums), stream())
+        ctx.save_for_backward(logits, div, align, target, ws, lse, sums)
+        ctx.pad_idx, ctx.eps, ctx.S = int(pad_idx), float(eps), S
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        logits, div, align, target, ws, lse, sums = ctx.saved_tensors
+        T_, B, V = logits.shape
+        d_logits, d_div = torch.empty_like(logits), torch.empty_like(div)
+        d_align = torch.empty_like(align)
+        g = d_loss.float().contiguous()         # (an expanded view after .sum(0)): a named local that outlives the launch below
+        call("gtos_copy_nll_ls_bwd", dt(logits), T_, B, V, ctx.S, ptr(logits), V, ptr(div), ptr(align), ptr(target), ctx.pad_idx,
+             ctx.eps, ptr(ws), ws.numel(), ptr(lse), ptr(sums), ptr(g), ptr(d_logits), ptr(d_div), ptr(d_align), stream())
+        del g
+        return d_logits, d_div, d_align, None, None, None, None
+
+
+def check_label_smoothing(eps):
+    """eps as a float; ValueError unless it is a real number (not a bool), finite and in [0, 1]."""
+    import math
+    import numbers
+    if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not math.isfinite(float(eps)) or not 0.0 <= float(eps) <= 1.0:
+        raise ValueError("label_smoothing must be a finite real number in [0, 1], got %r" % (eps,))
+    return float(eps)
+
+
+def copy_nll(logits, div, align, cp_seq, target, pad_idx, label_smoothing=0.0):
+    """Per-row loss of the generate/copy mixture; label_smoothing = eps of the reference's label_smoothed_nll_loss (0: plain NLL,
+    the CopyNllFn path)."""
+    eps = check_label_smoothing(label_smoothing)
+    if eps == 0.0:
+        return CopyNllFn.apply(logits, div, align, cp_seq, target, pad_idx)
+    return CopyNllLsFn.apply(logits, div, align, cp_seq, target, pad_idx, eps)
 
 
 def copy_log_likelihood(logits, div, align, cp_seq, tot_ext):

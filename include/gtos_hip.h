@@ -389,6 +389,25 @@ int gtos_copy_nll_bwd(int dtype, int T, int B, int V, int S, const void* logits,
 int gtos_copy_ll_fwd(int dtype, int T, int B, int V, int S, int tot_ext, const void* logits, int64_t ld_logits,
                      const void* div, const float* align, const int64_t* cp_seq, float* ll, void* stream);
 
+/* ---- Label-smoothed copy loss (ABI 24; csrc/copy_ls.hip, per-row arithmetic in csrc/copy_ls_kernels.h): the reference's
+ * label_smoothed_nll_loss (generator/utils.py:54-63) on the ll row of generator/decoder.py:57-65, without that row.
+ * C = max(V, 1 + max(cp_seq)) for the whole batch; loss[t,b] = (1 - eps) * -ll[target] + eps / C * -sum_{k<C} ll[k] (0 where
+ * target == pad_idx), ll[k] = log(p_k + 1e-12) of the mixture of gtos_copy_ll_fwd.  SHAPES (-24 outside): S <= 4096, 0 <= eps <= 1,
+ * ws_words >= 4 + 3B + 4BS + B * ceil(V / 32).
+ * _prep (once per batch): C and the per-graph groups of equal copy ids into the int32 workspace ws, from cp_seq int64 [S,B].
+ * _fwd: loss [T,B], lse [T,B] and sums [T,B,2] (dloss/dgen_gate and dloss/dcopy_gate per unit upstream gradient) from logits [T,B,V]
+ *   (row stride ld_logits) and div [T,B,2] of `dtype`, align fp32 [T,B,S], target int64 [T,B] and ws.
+ * _bwd: d_logits [T,B,V] (dtype), d_div [T,B,2] (dtype) and d_align fp32 [T,B,S] (dense) from d_loss [T,B].
+ * Nothing [T,B,C]-sized is allocated and nothing is read back to the host: C lives in ws[0]. */
+int gtos_copy_nll_ls_prep(int B, int S, int V, const int64_t* cp_seq, int* ws, int64_t ws_words, void* stream);
+int gtos_copy_nll_ls_fwd(int dtype, int T, int B, int V, int S, const void* logits, int64_t ld_logits, const void* div,
+                         const float* align, const int64_t* target, int64_t pad_idx, float eps, const int* ws, int64_t ws_words,
+                         float* loss, float* lse, float* sums, void* stream);
+int gtos_copy_nll_ls_bwd(int dtype, int T, int B, int V, int S, const void* logits, int64_t ld_logits, const void* div,
+                         const float* align, const int64_t* target, int64_t pad_idx, float eps, const int* ws, int64_t ws_words,
+                         const float* lse, const float* sums, const float* d_loss, void* d_logits, void* d_div, float* d_align,
+                         void* stream);
+
 /* ---- Device-resident beam search (csrc/beam.hip; selection rule in csrc/beam_kernels.h), driven by
  * gtos_amd.search.beam_search_device: generator/search.py's Beam.update / Beam.completed / search_by_batch without a host round trip
  * per step.  B sentences x k fixed hypothesis slots, N = B*k, slot s belongs to sentence s / k.  SHAPES (-10 outside): k <= 32.
