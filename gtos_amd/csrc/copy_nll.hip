@@ -11,52 +11,11 @@
 // d(alignment) in one more pass.  The inference form (work=True: the full log-likelihood row incl. copy ids) is
 // copy_ll_kernel: probabilities into the output row, copy mass added with atomics (several concepts may share a copy
 // id), then the log in place -- the row stays in L2.
-#include "common.h"
+#include "copy_row.h"
 
 namespace {
 
-constexpr int NT = 256;
-
-__device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) {
-    v = is_max ? wave_max(v) : wave_sum(v);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();                               // red may still be read from a previous call
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float r = red[0];
-#pragma unroll
-    for (int w = 1; w < NT / 64; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-    return r;
-}
-
-template <typename T>
-__device__ __forceinline__ float row_lse(const T* __restrict__ lp, int V, bool vec, float* red) {
-    float m = -INFINITY;
-    if (vec) {
-        for (int v = threadIdx.x * 8; v < V; v += NT * 8) {
-            float x[8];
-            Vec8<T>::load(lp + v, x);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) m = fmaxf(m, x[e]);
-        }
-    } else {
-        for (int v = threadIdx.x; v < V; v += NT) m = fmaxf(m, to_f<T>(lp[v]));
-    }
-    m = block_reduce(m, true, red);
-    float s = 0.f;
-    if (vec) {
-        for (int v = threadIdx.x * 8; v < V; v += NT * 8) {
-            float x[8];
-            Vec8<T>::load(lp + v, x);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s += __expf(x[e] - m);
-        }
-    } else {
-        for (int v = threadIdx.x; v < V; v += NT) s += __expf(to_f<T>(lp[v]) - m);
-    }
-    s = block_reduce(s, false, red);
-    return m + __logf(s);
-}
+using namespace gtos_row;      // NT, block_reduce, row_lse: the row pass shared with csrc/copy_eval.hip
 
 struct NllArgs {
     int T, B, V, S;

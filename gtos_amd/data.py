@@ -389,6 +389,26 @@ def batchify_amr(items, vocabs, train=True, seed=0, n_threads=0, unk_rate=0., rn
     }, index_prep)   # train batches also carry 'relation_index' (eval batches are [n,n,B,K]: not factored)
 
 
+def batchify_targets(sequences, vocabs, local_token2idx):
+    """Decoder inputs and targets of given token-string lists, exactly as the two batchify functions build them for a batch's own
+    sentences (<STR> + tokens for the input, tokens + <END> for the target): ``sequences[i]`` is scored against the graph whose copy
+    table is ``local_token2idx[i]`` (token -> copy id; it takes precedence over the predictable vocabulary, and a string in neither
+    is <UNK>).  Returns int64 'token_in' [T,N], 'token_char_in' [T,N,chars], 'token_out' [T,N] (what Generator.score feeds)."""
+    if len(sequences) != len(local_token2idx):
+        raise ValueError("%d sequences for %d copy tables" % (len(sequences), len(local_token2idx)))
+    if not sequences:
+        raise ValueError("nothing to score: no target sequence")
+    for x in sequences:
+        if isinstance(x, str) or not all(isinstance(w, str) for w in x):
+            raise ValueError("a target is a list of token strings, got %r" % (x,))
+    aug = [[STR] + list(x) + [END] for x in sequences]
+    return {
+        'token_in': lists_to_tensor(aug, vocabs['token'])[:-1],
+        'token_char_in': strings_to_char_tensor(aug, vocabs['token_char'])[:-1],
+        'token_out': lists_to_tensor(aug, vocabs['predictable_token'], list(local_token2idx))[1:],
+    }
+
+
 class AMRLoader(object):
     """Batching policy of generator/data.py:269-316 (``DataLoader``): the preprocessed JSON items are shuffled and (stably)
     sorted by size ``n_tokens + n_concepts**2`` when training, packed greedily until a batch holds ``batch_size`` size units

@@ -74,6 +74,21 @@ class TokenGenerator(nn.Module):
         pad = self.vocabs['predictable_token'].padding_idx
         return ops.copy_nll(logits, div, alignment_weight, copy_seq, target, pad, self.label_smoothing).sum(0)
 
+    def evaluate(self, outs, graph_state, graph_padding_mask, copy_seq, target):
+        """Teacher-forced scoring beside ``forward``: the same attention, LayerNorm and projections without dropout, then ONE kernel
+        (gtos_copy_eval_fwd) for what a scorer reads off decoder.py's ll row: (nll [T,B] fp32 -- the plain -log p(target), label
+        smoothing does not enter --, pred [T,B] int32 = the row's argmax, p_pred [T,B] fp32)."""
+        cd = self.alignment_layer.compute_dtype
+        outs_s, outs = ops.split_stream(outs, cd)
+        x, alignment_weight = self.alignment_layer(outs, graph_state, graph_state, key_padding_mask=graph_padding_mask,
+                                                   need_weights=True)
+        ln = self.alignment_layer_norm
+        outs = ops.layer_norm_stream(outs_s, x, ln.weight, ln.bias, 0.0, ln.eps, cd)[1]
+        hidden = torch.tanh(ops.linear(outs, self.transfer.weight, self.transfer.bias))
+        logits = _padded_linear(hidden, self.generator)
+        div = _padded_linear(hidden, self.diverter)
+        return ops.copy_eval(logits, div, alignment_weight, copy_seq, target, self.vocabs['predictable_token'].padding_idx)
+
 
 class DecodeLayer(nn.Module):
     def __init__(self, vocabs, inference_layers, embed_dim, ff_embed_dim, num_heads, token_size, rel_size, dropout,
@@ -94,6 +109,13 @@ class DecodeLayer(nn.Module):
         token_loss = self.token_generator(outs, graph_state, graph_padding_mask, copy_seq, target=target, work=False)
         token_tot = snt_padding_mask.size(0) - snt_padding_mask.float().sum(0)
         return (token_loss / token_tot).mean()
+
+    def evaluate(self, probe, graph_state, snt_state, graph_padding_mask, snt_padding_mask, attn_mask, copy_seq, target):
+        """``forward`` up to the token generator, then TokenGenerator.evaluate: (nll, pred, p_pred) per target position.  Call it
+        in eval mode under no_grad (Generator.score does)."""
+        outs = self.inference_core(probe, kv=snt_state, self_padding_mask=snt_padding_mask, self_attn_mask=attn_mask,
+                                   external_memories=graph_state, external_padding_mask=graph_padding_mask)
+        return self.token_generator.evaluate(outs, graph_state, graph_padding_mask, copy_seq, target)
 
     def step(self, probe, token_row, caches, mem):
         """Log-likelihoods of the next token, [1,N,V+ext] (decoder.py:85-87 with work=True), for N live hypotheses.

@@ -8,6 +8,7 @@ exact same function as the reference's ``relation.index_select(0, idx).view(n,n,
 (decode_step_batched): the reference re-projects the whole prefix in every layer at every step.  ``decode_step`` keeps the
 reference's signature (generator.py:119) for callers that bring their own search loop.
 """
+import collections
 import ctypes
 import math
 import numbers
@@ -38,6 +39,21 @@ def check_sampling(samples, temperature, top_k, top_p, seed):
         raise ValueError("top_p must lie in (0, 1] and be > 0 in fp32, got %r" % (top_p,))
     if seed is not None and (isinstance(seed, bool) or not isinstance(seed, numbers.Integral)):
         raise ValueError("seed must be an integer or None, got %r" % (seed,))
+
+
+class Scores(collections.namedtuple("Scores", "sentence_ll tokens correct token_ll pred graph_of")):
+    """What Generator.score returns, all DEVICE tensors over N scored sequences of at most T target positions (tokens + <END>):
+    sentence_ll [N] fp64 = log p(sequence | graph), tokens [N] int32 (target positions), correct [N] int32 (positions whose argmax
+    is the target), token_ll [T,N] fp32 (0 at padding), pred [T,N] int32 (the argmax column of every position, over the vocabulary and
+    the graph's copy ids), graph_of [N] int64 (the graph each sequence was scored against)."""
+    vocab = None         # the predictable-token vocabulary (Generator.score sets it on the instance)
+
+    def strings(self, data, vocab=None):
+        """Host side, on demand: ``pred`` as token strings, one list per sequence cut to its ``tokens`` positions -- a copy id through
+        the graph's ``data['local_idx2token']``, anything else through the predictable-token vocabulary."""
+        local, vocab = data['local_idx2token'], vocab if vocab is not None else self.vocab
+        pred, owner, n_tok = self.pred.t().tolist(), self.graph_of.tolist(), self.tokens.tolist()
+        return [[local[g][i] if i in local[g] else vocab.idx2token(i) for i in row[:n]] for row, g, n in zip(pred, owner, n_tok)]
 
 
 class Generator(nn.Module):
@@ -195,6 +211,97 @@ class Generator(nn.Module):
             else:
                 beam_search(self, beams, memory)
         return beams
+
+    # ------------------------------------------------------------------------------------------------ teacher-forced scoring
+    def _score_sequences(self, data, targets):
+        """(sequences, graph of each sequence, copy table of each sequence) of ``score(data, targets)``; ValueError on anything
+        that is not one token-string list, or a list of them, per graph."""
+        B = data['concept'].size(1)
+        if isinstance(targets, str) or len(targets) != B:
+            raise ValueError("targets holds one entry per graph: %d graphs, got %r entries"
+                             % (B, len(targets) if not isinstance(targets, str) else targets))
+        tables = data.get('local_token2idx')
+        if tables is None:
+            inverse = data.get('local_idx2token')
+            if inverse is None:
+                raise ValueError("scoring given targets needs the batch's copy table: 'local_token2idx' or 'local_idx2token'")
+            tables = [{w: i for i, w in t.items()} for t in inverse]
+        seqs, owner = [], []
+        for b, entry in enumerate(targets):
+            if isinstance(entry, str) or not isinstance(entry, (list, tuple)):
+                raise ValueError("targets[%d] is a token-string list or a list of them, got %r" % (b, entry))
+            nbest = [entry] if entry and isinstance(entry[0], str) else entry      # (an empty entry: nothing to score for this graph)
+            for x in nbest:
+                if isinstance(x, str) or not isinstance(x, (list, tuple)) or not all(isinstance(w, str) for w in x):
+                    raise ValueError("targets[%d]: a target is a list of token strings, got %r" % (b, x))
+                seqs.append(list(x))
+                owner.append(b)
+        return seqs, owner, [tables[b] for b in owner]
+
+    def score_rows(self, data, targets=None):
+        """The device part of ``score``: (nll [T,N] fp32, pred [T,N] int32, p_pred [T,N] fp32, target [T,N] int64, graph_of [N]
+        int64).  Eval mode and no autograd whatever the module's state, which is left as found; no dropout seed is drawn."""
+        given = None if targets is None else self._score_sequences(data, targets)
+        modes = [(m, m.training) for m in self.modules()]
+        enc = self.relation_encoder
+        trie_was = getattr(enc, "trie_in_eval", True)
+        try:
+            self.eval()
+            # the whole bank in one packed pass, as in training: the trie evaluation eval mode otherwise takes is a chain of small
+            # launches per trie level, three times slower at C2 where one pass over all rows is wanted
+            enc.trie_in_eval = False
+            with torch.no_grad():
+                return self._score_rows(data, given)
+        finally:
+            enc.trie_in_eval = trie_was
+            for m, was in modes:
+                m.training = was
+
+    def _score_rows(self, data, given):
+        dev, pad = data['concept'].device, self.vocabs['predictable_token'].padding_idx
+        if given is not None and not given[0]:          # every n-best list empty: nothing to launch
+            z = lambda dt: torch.zeros((0, 0), dtype=dt, device=dev)        # noqa: E731
+            return z(torch.float32), z(torch.int32), z(torch.float32), z(torch.int64), torch.zeros(0, dtype=torch.int64, device=dev)
+        concept_repr, concept_mask, probe = self.encode_step(data, train=False)
+        concept_repr, cp_seq = concept_repr.contiguous(), data['cp_seq']
+        if given is None:
+            token_in, token_char_in, target = data['token_in'], data['token_char_in'], data['token_out']
+            graph_of = torch.arange(concept_repr.size(1), device=dev)
+        else:
+            from .data import batchify_targets
+            seqs, owner, tables = given
+            built = batchify_targets(seqs, self.vocabs, tables)
+            token_in, token_char_in, target = (built[k].to(dev) for k in ('token_in', 'token_char_in', 'token_out'))
+            # the graph is encoded once; its memory is gathered per sequence, as search.slot_memory gathers it per slot
+            graph_of = torch.tensor(owner, dtype=torch.int64).to(dev)
+            sel = lambda v: v.index_select(1, graph_of)                      # noqa: E731
+            concept_repr, concept_mask, cp_seq, probe = sel(concept_repr), sel(concept_mask), sel(cp_seq), sel(probe)
+        pos = self.token_position(token_in).to(self.compute_dtype)
+        token_repr = self.embed_scale * self.token_encoder(token_in, token_char_in) + pos
+        ln = self.token_embed_layer_norm
+        token_repr = ops.layer_norm_residual(token_repr, None, ln.weight, ln.bias, 0.0, ln.eps)
+        token_mask = torch.eq(token_in, self.vocabs['token'].padding_idx)
+        attn_mask = self.self_attn_mask(token_in.size(0))
+        token_repr = self.snt_encoder(token_repr, self_padding_mask=token_mask, self_attn_mask=attn_mask,
+                                      external_memories=concept_repr, external_padding_mask=concept_mask)
+        token_repr = ops.split_stream(token_repr, self.compute_dtype)[1]
+        nll, pred, p_pred = self.decoder.evaluate(probe.expand_as(token_repr), concept_repr, token_repr, concept_mask, token_mask,
+                                                  attn_mask, cp_seq.contiguous(), target)
+        return nll, pred, p_pred, target, graph_of
+
+    def score(self, data, targets=None):
+        """Teacher-forced log-likelihoods: of the batch's own sentences (``data['token_out']`` given ``data['token_in']``), or of
+        ``targets`` -- per graph one token-string list or a list of them (an n-best list; lengths may differ, a list may be empty),
+        without <STR> / <END>.  The graph is encoded once; the strings become ids through the vocabularies and the graph's copy table
+        as the loader builds them (data.batchify_targets).  A score is the plain log-likelihood: label smoothing does not enter, the
+        module runs as in eval mode under no_grad (its mode is left as found), no seed is drawn and the host reads nothing.  Returns
+        ``Scores`` (device tensors)."""
+        nll, pred, _, target, graph_of = self.score_rows(data, targets)
+        live = target.ne(self.vocabs['predictable_token'].padding_idx)
+        out = Scores(sentence_ll=-nll.double().sum(0), tokens=live.sum(0).to(torch.int32),
+                     correct=(pred.eq(target) & live).sum(0).to(torch.int32), token_ll=-nll, pred=pred, graph_of=graph_of)
+        out.vocab = self.vocabs['predictable_token']
+        return out
 
     # ---- fixed-slot decoding for gtos_amd.search.beam_search_device
     def search_tables(self, local_idx2token, tot):

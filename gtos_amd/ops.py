@@ -1258,6 +1258,54 @@ def copy_log_likelihood(logits, div, align, cp_seq, tot_ext):
     return ll
 
 
+def copy_eval(logits, div, align, cp_seq, target, pad_idx, out=None):
+    """Teacher-forced scoring of the generate/copy mixture (gtos_copy_eval_fwd, no autograd): per row (t, b)
+    nll [T,B] fp32 (bitwise the forward of copy_nll without label smoothing), pred [T,B] int32 = the argmax column of the mixture
+    over the vocabulary and the graph's copy ids (equal values: the lower column) and p_pred [T,B] fp32 = its probability -- what
+    copy_log_likelihood + max + gather give, without the [T,B,V+copies] row.  ``out``: (nll, pred, p_pred) to write into."""
+    require_cuda(logits, div, align, cp_seq, target)
+    T_, B, V = logits.shape
+    S = cp_seq.shape[0]
+    logits, div = logits.contiguous(), div.contiguous()
+    align = align.float().contiguous()
+    cp_seq, target = cp_seq.contiguous(), target.contiguous()
+    if cp_seq.dtype != torch.int64 or target.dtype != torch.int64 or tuple(target.shape) != (T_, B):
+        raise _lib.GtosHipError("copy_eval: cp_seq [S,B] and target [T,B] are int64")
+    if out is None:
+        nll = torch.empty((T_, B), dtype=torch.float32, device=logits.device)
+        pred = torch.empty((T_, B), dtype=torch.int32, device=logits.device)
+        p_pred = torch.empty_like(nll)
+    else:
+        nll, pred, p_pred = out
+        require_cuda(nll, pred, p_pred)
+        for t, d in ((nll, torch.float32), (pred, torch.int32), (p_pred, torch.float32)):
+            if t.dtype != d or tuple(t.shape) != (T_, B) or not t.is_contiguous():
+                raise _lib.GtosHipError("copy_eval: out = (nll fp32, pred int32, p_pred fp32), each contiguous [T,B]")
+    call("gtos_copy_eval_fwd", dt(logits), T_, B, V, S, ptr(logits), V, ptr(div), ptr(align), ptr(cp_seq), ptr(target),
+         int(pad_idx), ptr(nll), ptr(pred), ptr(p_pred), stream())
+    return nll, pred, p_pred
+
+
+def eval_accumulate(nll, pred, target, pad_idx, totals):
+    """gtos_eval_accumulate: folds one batch's copy_eval result into the running ``totals`` fp64 [5] = (sum nll, tokens, correct,
+    sentences, sum over sentences of nll / tokens) on the device, in a fixed order, and returns the batch's per-sentence
+    (sent_nll fp64 [B], sent_tokens int32 [B], sent_correct int32 [B]).  No host read."""
+    require_cuda(nll, pred, target, totals)
+    T_, B = nll.shape
+    if (nll.dtype != torch.float32 or pred.dtype != torch.int32 or target.dtype != torch.int64 or tuple(pred.shape) != (T_, B)
+            or tuple(target.shape) != (T_, B)):
+        raise _lib.GtosHipError("eval_accumulate: nll fp32, pred int32 and target int64, all [T,B]")
+    if totals.dtype != torch.float64 or totals.numel() != 5 or not totals.is_contiguous():
+        raise _lib.GtosHipError("eval_accumulate: totals is a contiguous fp64 tensor of 5 elements")
+    nll, pred, target = nll.contiguous(), pred.contiguous(), target.contiguous()
+    sent_nll = torch.empty(B, dtype=torch.float64, device=nll.device)
+    sent_tokens = torch.empty(B, dtype=torch.int32, device=nll.device)
+    sent_correct = torch.empty(B, dtype=torch.int32, device=nll.device)
+    call("gtos_eval_accumulate", T_, B, ptr(nll), ptr(pred), ptr(target), int(pad_idx), ptr(sent_nll), ptr(sent_tokens),
+         ptr(sent_correct), ptr(totals), stream())
+    return sent_nll, sent_tokens, sent_correct
+
+
 # ---------------------------------------------------------------------------------------------- device-resident beam search
 # (csrc/beam.hip; gtos_amd.search.beam_search_device drives them)
 def beam_topk(ll, k):

@@ -14,6 +14,7 @@ Counterpart of the hot loop of /root/reference/generator/train.py:136-154: forwa
   * dropout streams are decorrelated across ranks by seeding the hash stream with base + rank after the (identical)
     weight initialisation, like train.py:113-116.
 """
+import math
 import os
 import time
 
@@ -217,6 +218,35 @@ class Trainer:
             ev.record()
             self._done_events.append(ev)
         return res.value() if sync else res
+
+    def evaluate(self, batches, totals=None):
+        """Held-out evaluation, teacher-forced: ``Generator.score_rows`` (one gtos_copy_eval_fwd) and one gtos_eval_accumulate per
+        batch into one device buffer of five fp64 totals, ONE host read at the end; data parallel, each rank passes its own shard of
+        batches and the totals are summed by one all-reduce before that read.  Returns ``eval_metrics``: nll_per_token, perplexity,
+        accuracy, tokens, sentences and loss (the reference-normalised mean, comparable with the training loss).  ``totals`` (fp64
+        [5] on the device) continues a running evaluation.  The training state is left alone: parameters, bf16 mirror, gradient
+        bucket, Adam moments, counters, the seed counter and the model's train / eval mode."""
+        if totals is None:
+            totals = torch.zeros(5, dtype=torch.float64, device=self.flat.param.device)
+        pad = self.model.vocabs['predictable_token'].padding_idx
+        for batch in batches:
+            nll, pred, _, target, _ = self.model.score_rows(batch)
+            if nll.numel():
+                ops.eval_accumulate(nll, pred, target, pad, totals)
+        if self.world_size > 1:
+            dist.all_reduce(totals, op=dist.ReduceOp.SUM)       # the one collective of an evaluation
+        return eval_metrics(totals.tolist())                    # ... and its one host read
+
+
+def eval_metrics(totals):
+    """The dict of Trainer.evaluate from the five totals of gtos_eval_accumulate (sum nll, tokens, correct, sentences, sum over
+    sentences of nll / tokens): corpus NLL per token, its perplexity, token accuracy, and ``loss`` = the reference-normalised mean
+    (mean over sentences of the per-sentence mean NLL, decoder.py:91-94: what ``forward`` reports).  NaN where nothing was scored."""
+    s, n, ok, sents, norm = (float(v) for v in totals)
+    per_token = s / n if n else float("nan")
+    return {"nll_per_token": per_token, "perplexity": math.exp(min(per_token, 700.0)) if n else float("nan"),
+            "accuracy": ok / n if n else float("nan"), "tokens": int(n), "sentences": int(sents),
+            "loss": norm / sents if sents else float("nan")}
 
 
 class GraphedStep:

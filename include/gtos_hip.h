@@ -408,6 +408,22 @@ int gtos_copy_nll_ls_bwd(int dtype, int T, int B, int V, int S, const void* logi
                          const float* lse, const float* sums, const float* d_loss, void* d_logits, void* d_div, float* d_align,
                          void* stream);
 
+/* ---- Teacher-forced scoring (ABI 25; csrc/copy_eval.hip, the rule in csrc/copy_eval_kernels.h): what a scorer takes from the ll row
+ * of generator/decoder.py:42-60 (work=True) -- the gather at the target (decoder.py:62-64) and the row's argmax -- without that row.
+ * Operands as gtos_copy_nll_fwd.  SHAPES (-24 outside): V >= 1, 0 <= S <= 4096, ld_logits >= V; -23 for a null pointer.
+ * _copy_eval_fwd: nll[t,b] fp32, bitwise what gtos_copy_nll_fwd writes (0 where target == pad_idx); pred[t,b] int32 = argmax_k of the
+ *   mixture p_k = gen_gate * softmax(logits)_k [k < V] + copy_gate * sum_{s: cp_seq[s,b] == k} align[t,b,s], equal values to the lower
+ *   column (the rule of gtos_beam_topk), and p_pred[t,b] fp32 = that maximum.  A padded row still gets its pred / p_pred.
+ * _eval_accumulate (one workgroup, fixed summation order): per column b the fp64 sum of nll[:, b] over the non-pad targets in t order,
+ *   their count and the count of pred == target among them into sent_nll fp64 [B], sent_tokens / sent_correct int32 [B]; and ADDS to
+ *   totals fp64 [5] = (sum nll, tokens, correct, sentences, sum_b sent_nll[b] / sent_tokens[b]) over the columns in column order.  The
+ *   last is the sum behind the reference's loss normalisation (decoder.py:91-94); a column without a non-pad target is no sentence. */
+int gtos_copy_eval_fwd(int dtype, int T, int B, int V, int S, const void* logits, int64_t ld_logits, const void* div,
+                       const float* align, const int64_t* cp_seq, const int64_t* target, int64_t pad_idx, float* nll,
+                       int* pred, float* p_pred, void* stream);
+int gtos_eval_accumulate(int T, int B, const float* nll, const int* pred, const int64_t* target, int64_t pad_idx,
+                         double* sent_nll, int* sent_tokens, int* sent_correct, double* totals, void* stream);
+
 /* ---- Device-resident beam search (csrc/beam.hip; selection rule in csrc/beam_kernels.h), driven by
  * gtos_amd.search.beam_search_device: generator/search.py's Beam.update / Beam.completed / search_by_batch without a host round trip
  * per step.  B sentences x k fixed hypothesis slots, N = B*k, slot s belongs to sentence s / k.  SHAPES (-10 outside): k <= 32.
