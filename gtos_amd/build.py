@@ -19,16 +19,16 @@ def _stale(target, deps):
 
 
 def _deps(obj, fallback):
-    """Headers the object was compiled from, read from the depfile its last compilation wrote (-MMD); without one, the header the
+    """Headers the object was compiled from, read from the depfile its last compilation wrote (-MMD); without one, the headers the
     source is known to include.  Only headers inside the repository are tracked (the ROCm headers do not change under us)."""
     dfile = obj[:-2] + ".d"
     root = os.path.dirname(os.path.dirname(CSRC))
     try:
         words = open(dfile).read().replace("\\\n", " ").split()
     except OSError:
-        return [fallback]
+        return fallback
     deps = [w for w in words[1:] if w.endswith((".h", ".hpp")) and os.path.abspath(w).startswith(root) and os.path.exists(w)]
-    return deps or [fallback]
+    return deps or fallback
 
 
 HOST_SRCS = [os.path.join(os.path.dirname(CSRC), "csrc_host", f) for f in ("relbatch.cpp", "pathtrie.cpp", "relindex.cpp")]
@@ -51,15 +51,15 @@ def build_host(force=False, verbose=True):
 def build(force=False, verbose=True):
     build_host(force, verbose)
     own_hdr = {"pathtrie_dev.hip": "trie_kernels.h", "relbatch_dev.hip": "relbatch_kernels.h",
-               "relindex_dev.hip": "relindex_kernels.h", "beam.hip": "beam_kernels.h",
-               "sample.hip": "sample_kernels.h", "copy_ls.hip": "copy_ls_kernels.h",
+               "relindex_dev.hip": "relindex_kernels.h", "beam.hip": "beam_kernels.h slot_kernels.h slot_device.h",
+               "sample.hip": "sample_kernels.h slot_kernels.h slot_device.h", "copy_ls.hip": "copy_ls_kernels.h",
                "copy_nll.hip": "copy_row.h", "copy_eval.hip": "copy_eval_kernels.h"}     # the others include common.h
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + _deps(o, os.path.join(CSRC, own_hdr.get(src, "common.h")))):
+        if force or _stale(o, [s] + _deps(o, [os.path.join(CSRC, h) for h in own_hdr.get(src, "common.h").split()])):
             flags = [f for f in FLAGS if f not in ("-ffast-math", "-fno-finite-math-only")] + ["-ffp-contract=off"] if src in EXACT_FP else FLAGS
             cmd = [HIPCC] + flags + ["-MMD", "-MF", o[:-2] + ".d", "-c", s, "-o", o]
             if verbose:

@@ -2,74 +2,26 @@
 // rule in csrc/beam_kernels.h, shared with the host check), and the reorder of the self-attention caches by parent slot together with
 // the next step's input token ids and character rows.  Nothing here synchronises with the host; the per-beam state, back-pointers and
 // completions stay on the device until the search ends.
-#include "common.h"
 #include "beam_kernels.h"
-
-#include <limits.h>
+#include "slot_device.h"
 
 using namespace gtos_beam;
 
 namespace {
 
-constexpr int NT = 256;                 // 4 waves
+static_assert(MAX_K <= TOPK_MAX, "beam_topk_kernel ranks its rows with row_topk");
 
-// (value, index) a goes before b: larger value first, equal values lower index first
-__device__ __forceinline__ bool tk_before(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
-
-// One workgroup per row.  Every lane keeps its KM best (value, column) in registers, sorted, scanning columns lane, lane + NT, ...;
-// each wave then pops its k best by k butterfly arg-max rounds over the lanes' heads, and the 4 x k wave winners are ranked in LDS.
+// One workgroup per row: row_topk over every column, the sorted list stored
 template <int KM>
 __global__ __launch_bounds__(NT) void beam_topk_kernel(int tot, int k, const float* __restrict__ ll, int64_t ld,
                                                        float* __restrict__ val, int* __restrict__ idx) {
-    __shared__ float sv[NT / 64][MAX_K];
-    __shared__ int si[NT / 64][MAX_K];
-    const int row = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const float* x = ll + (int64_t)row * ld;
-    float v[KM];
-    int ix[KM];
-#pragma unroll
-    for (int j = 0; j < KM; ++j) { v[j] = -__builtin_inff(); ix[j] = INT_MAX; }
-    for (int c = threadIdx.x; c < tot; c += NT) {
-        const float y = x[c];
-        if (tk_before(y, c, v[KM - 1], ix[KM - 1])) {
-            v[KM - 1] = y; ix[KM - 1] = c;
-#pragma unroll
-            for (int j = KM - 1; j > 0; --j) {
-                if (tk_before(v[j], ix[j], v[j - 1], ix[j - 1])) {
-                    const float tv = v[j]; v[j] = v[j - 1]; v[j - 1] = tv;
-                    const int ti = ix[j]; ix[j] = ix[j - 1]; ix[j - 1] = ti;
-                }
-            }
-        }
-    }
-    for (int r = 0; r < k; ++r) {
-        float bv = v[0];
-        int bi = ix[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(bi, o);
-            if (tk_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (ix[0] == bi) {             // the winning lane pops its head (columns are unique; an all-sentinel wave pops sentinels)
-#pragma unroll
-            for (int j = 0; j < KM - 1; ++j) { v[j] = v[j + 1]; ix[j] = ix[j + 1]; }
-            v[KM - 1] = -__builtin_inff(); ix[KM - 1] = INT_MAX;
-        }
-        if (lane == 0) { sv[w][r] = bv; si[w][r] = bi; }
-    }
-    __syncthreads();
-    const int n = (NT / 64) * k;
-    if (threadIdx.x < n) {
-        const int wi = threadIdx.x / k, ri = threadIdx.x % k;
-        const float a = sv[wi][ri];
-        const int ai = si[wi][ri];
-        int rank = 0;
-        for (int q = 0; q < n; ++q) rank += tk_before(sv[q / k][q % k], si[q / k][q % k], a, ai);
-        if (rank < k && ai != INT_MAX) {
-            val[(int64_t)row * k + rank] = a;
-            idx[(int64_t)row * k + rank] = ai;
-        }
+    __shared__ float lv[MAX_K];
+    __shared__ int lc[MAX_K];
+    const int row = blockIdx.x;
+    row_topk<KM>(ll + (int64_t)row * ld, tot, k, [](int, float) { return true; }, lv, lc);
+    if (threadIdx.x < k && lc[threadIdx.x] != INT_MAX) {
+        val[(int64_t)row * k + threadIdx.x] = lv[threadIdx.x];
+        idx[(int64_t)row * k + threadIdx.x] = lc[threadIdx.x];
     }
 }
 
@@ -89,18 +41,17 @@ struct AdvanceArgs {
     int* active;
 };
 
-// One workgroup per beam.  active[3] rotates: step t reads active[t % 3] (did any not-done beam have a live slot when this iteration
-// started?), ORs its own answer into active[(t + 1) % 3] and clears active[(t + 2) % 3] for step t + 1.  An iteration that does
-// not run (search.py's loop would have stopped) changes nothing, and the flag stays 0 from then on.
+// One workgroup per beam.  The active[3] rotation of csrc/slot_kernels.h; the flag: did any not-done beam have a live slot when this
+// iteration started?
 __global__ __launch_bounds__(NT) void beam_advance_kernel(AdvanceArgs a) {
     __shared__ double ps[MAX_K * MAX_K];
     __shared__ int pt[MAX_K * MAX_K];
     __shared__ uint8_t pf[MAX_K * MAX_K];
     __shared__ int order[MAX_K];
     const int b = blockIdx.x, t = a.t;
-    if (b == 0 && threadIdx.x == 0) a.active[(t + 2) % 3] = 0;
+    if (b == 0 && threadIdx.x == 0) a.active[active_clear(t)] = 0;
     const int* st = a.state + (int64_t)b * BS_WORDS;
-    if (!a.active[t % 3] || st[BS_DONE]) return;
+    if (!a.active[active_read(t)] || st[BS_DONE]) return;
     const int P = st[BS_NLIVE] * a.k;
     const int m = cut_size(P, a.k, st[BS_NCOMP]);
     for (int p = threadIdx.x; p < P; p += NT)
@@ -115,14 +66,14 @@ __global__ __launch_bounds__(NT) void beam_advance_kernel(AdvanceArgs a) {
         const int64_t N = (int64_t)a.B * a.k;
         if (place(b, a.k, a.min_t, a.max_t, order, m, ps, pt, pf, t, a.state, a.bp_parent + t * N, a.bp_token + t * N, a.slot_score,
                   a.comp_step, a.comp_parent, a.comp_score))
-            atomicOr(a.active + (t + 1) % 3, 1);
+            atomicOr(a.active + active_set(t), 1);
     }
 }
 
 constexpr int MAX_CACHES = 32;
 
 struct ReorderArgs {
-    int n, N, k, t, V, tot, C;
+    int n, N, k, t, V, tot;
     int64_t q;                          // 16-byte pieces per cache row
     const uint4* src[MAX_CACHES];
     uint4* dst[MAX_CACHES];
@@ -130,14 +81,7 @@ struct ReorderArgs {
     const int* bp_token_t;
     const int* state;
     const int* active_t;                // the flag step t's advance read
-    const int64_t* tok_shared;
-    const int64_t* tok_local;
-    const int64_t* char_shared;
-    const int64_t* char_local;
-    int64_t dead_tok;
-    const int64_t* dead_char;
-    int64_t* tok_out;
-    int64_t* char_out;
+    NextInput next;
 };
 
 __device__ __forceinline__ bool slot_live(const ReorderArgs& a, int s) {
@@ -151,19 +95,10 @@ __global__ __launch_bounds__(NT) void beam_reorder_kernel(ReorderArgs a) {
     const bool act = *a.active_t != 0;
     const int64_t stride = (int64_t)gridDim.x * NT;
     if ((int)blockIdx.y == a.n) {
-        for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < (int64_t)a.N * (a.C + 1); e += stride) {
-            const int s = (int)(e / (a.C + 1)), c = (int)(e % (a.C + 1)) - 1;      // c == -1: the token id
-            int64_t out;
-            if (act && slot_live(a, s)) {
-                const int id = a.bp_token_t[s];
-                const int64_t lid = (int64_t)(s / a.k) * (a.tot - a.V) + (id - a.V);
-                if (c < 0) out = id < a.V ? a.tok_shared[id] : a.tok_local[lid];
-                else out = id < a.V ? a.char_shared[(int64_t)id * a.C + c] : a.char_local[lid * a.C + c];
-            } else {
-                out = c < 0 ? a.dead_tok : a.dead_char[c];
-            }
-            if (c < 0) a.tok_out[s] = out;
-            else a.char_out[(int64_t)s * a.C + c] = out;
+        const int C1 = a.next.C + 1;
+        for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < (int64_t)a.N * C1; e += stride) {
+            const int s = (int)(e / C1);
+            write_next_input(a.next, a.V, a.tot, s / a.k, s, (int)(e % C1) - 1, act && slot_live(a, s) ? a.bp_token_t[s] : -1);
         }
         return;
     }
@@ -187,12 +122,10 @@ extern "C" int gtos_beam_topk(int rows, int tot, int k, const float* ll, int64_t
     if (rows <= 0) return 0;
     if (k < 1 || k > MAX_K || tot < k || ld < tot) return -10;
     if (!ll || !val || !idx) return -23;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 g((unsigned)rows), blk(NT);
-    if (k <= 4) hipLaunchKernelGGL(beam_topk_kernel<4>, g, blk, 0, s, tot, k, ll, ld, val, idx);
-    else if (k <= 8) hipLaunchKernelGGL(beam_topk_kernel<8>, g, blk, 0, s, tot, k, ll, ld, val, idx);
-    else if (k <= 16) hipLaunchKernelGGL(beam_topk_kernel<16>, g, blk, 0, s, tot, k, ll, ld, val, idx);
-    else hipLaunchKernelGGL(beam_topk_kernel<32>, g, blk, 0, s, tot, k, ll, ld, val, idx);
+    dispatch_km(k, [&](auto km) {
+        hipLaunchKernelGGL(beam_topk_kernel<decltype(km)::value>, dim3((unsigned)rows), dim3(NT), 0, static_cast<hipStream_t>(stream),
+                           tot, k, ll, ld, val, idx);
+    });
     GTOS_CHECK_LAUNCH();
     return 0;
 }
@@ -225,20 +158,17 @@ extern "C" int gtos_beam_reorder(int n_caches, void* const* src, void* const* ds
     if (n_caches < 0 || n_caches > MAX_CACHES || row_bytes <= 0 || row_bytes % 16 || k < 1 || k > MAX_K || N % k || t < 0 ||
         t >= max_time_step || V < 1 || tot < V || C < 1)
         return -10;
-    if ((n_caches && (!src || !dst)) || !bp_parent || !bp_token || !beam_state || !active || !tok_shared || !char_shared ||
-        (tot > V && (!tok_local || !char_local)) || !dead_char || !tok_out || !char_out)
-        return -23;
     ReorderArgs a{};
-    a.n = n_caches; a.N = N; a.k = k; a.t = t; a.V = V; a.tot = tot; a.C = C; a.q = row_bytes / 16;
+    a.next = NextInput{tok_shared, tok_local, char_shared, char_local, dead_tok, dead_char, C, tok_out, char_out};
+    if ((n_caches && (!src || !dst)) || !bp_parent || !bp_token || !beam_state || !active || !next_input_ok(a.next, V, tot)) return -23;
+    a.n = n_caches; a.N = N; a.k = k; a.t = t; a.V = V; a.tot = tot; a.q = row_bytes / 16;
     for (int i = 0; i < n_caches; ++i) {
         if (!src[i] || !dst[i] || (uintptr_t)src[i] % 16 || (uintptr_t)dst[i] % 16 || src[i] == dst[i]) return -25;
         a.src[i] = static_cast<const uint4*>(src[i]);
         a.dst[i] = static_cast<uint4*>(dst[i]);
     }
     a.bp_parent_t = bp_parent + (int64_t)t * N; a.bp_token_t = bp_token + (int64_t)t * N; a.state = beam_state;
-    a.active_t = active + t % 3;
-    a.tok_shared = tok_shared; a.tok_local = tok_local; a.char_shared = char_shared; a.char_local = char_local;
-    a.dead_tok = dead_tok; a.dead_char = dead_char; a.tok_out = tok_out; a.char_out = char_out;
+    a.active_t = active + active_read(t);
     const int64_t work = (int64_t)(t + 1) * N * a.q;
     const int64_t blocks = (work + NT - 1) / NT;
     const unsigned gx = (unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks);

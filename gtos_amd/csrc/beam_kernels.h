@@ -3,30 +3,20 @@
 // gtos_amd.search.Beam.advance / Beam.completed on random pools, step counters included.  The kernel runs the same helpers:
 // the pool is filled and ranked by many threads (beam_pool_entry, beam_rank), the cut is placed by one (beam_place).
 //
-// Slots: B beams of k slots each, N = B*k; slot s belongs to beam s / k.  After an advance the live hypotheses of beam b are its
+// Slots as in csrc/slot_kernels.h, one beam per graph.  After an advance the live hypotheses of beam b are its
 // slots b*k .. b*k + n_live - 1, in the order Beam.advance returns them.  The pool of an advance is the candidates of the live
 // slots in (slot, candidate rank) order: position p = j*k + r for live slot j and rank r, k candidates per slot.
 #pragma once
-#include <stdint.h>
+#include "slot_kernels.h"
 
-#if defined(__HIPCC__)
-#define GTOS_BEAM_HD __host__ __device__ inline
-#else
-#define GTOS_BEAM_HD inline
-#endif
+#define GTOS_BEAM_HD GTOS_SLOT_HD
 
 namespace gtos_beam {
 
-// string class of a token id, from the per-batch tables (Beam.advance compares the STRING with <UNK> / <END>)
-enum { TOK_PLAIN = 0, TOK_UNK = 1, TOK_END = 2 };
+using namespace gtos_slot;              // token classes, token_flag, the active[3] rotation
 // per-beam state words, int32 [B, BS_WORDS]
 enum { BS_STEPS = 0, BS_NCOMP = 1, BS_NLIVE = 2, BS_DONE = 3, BS_WORDS = 4 };
 constexpr int MAX_K = 32;
-
-// ids < V: shared table (the predictable-token vocabulary); ids in [V, tot): the beam's graph's copy table
-GTOS_BEAM_HD uint8_t token_flag(const uint8_t* flag_shared, const uint8_t* flag_local, int V, int tot, int b, int id) {
-    return id < V ? flag_shared[id] : flag_local[(int64_t)b * (tot - V) + (id - V)];
-}
 
 // Python's `float('-inf') if token == UNK else base + ll`: base is the parent's fp64 score, ll an fp32 log-likelihood
 GTOS_BEAM_HD double cand_score(double base, float ll, uint8_t flag) {

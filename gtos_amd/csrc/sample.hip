@@ -3,20 +3,17 @@
 // pass, a threshold bisection for top-p with fp64 block sums over the row, a Gumbel arg-max, then the slot's bookkeeping and its next
 // input.  Rows are read from global memory as often as the passes need (they stay in L2 / MALL); nothing is staged in LDS but the
 // partial results.  Nothing here synchronises with the host.
-#include "common.h"
 #include "sample_kernels.h"
-
-#include <limits.h>
+#include "slot_device.h"
 
 using namespace gtos_sample;
 
 namespace {
 
-constexpr int NT = 256;                 // 4 waves
-constexpr int NW = NT / 64;
+static_assert(MAX_TOPK <= TOPK_MAX, "select_topk ranks its row with row_topk");
 
 struct SampleArgs {
-    int N, k, t, V, tot, min_t, max_t, top_k, C;
+    int N, k, t, V, tot, min_t, max_t, top_k;
     double T, top_p;
     uint64_t seed;
     const float* ll;
@@ -28,14 +25,7 @@ struct SampleArgs {
     int* state;
     int* tokens;
     int* active;
-    const int64_t* tok_shared;
-    const int64_t* tok_local;
-    const int64_t* char_shared;
-    const int64_t* char_local;
-    int64_t dead_tok;
-    const int64_t* dead_char;
-    int64_t* tok_out;
-    int64_t* char_out;
+    NextInput next;
 };
 
 __device__ __forceinline__ bool col_allowed(const SampleArgs& a, int b, int c, float y) {
@@ -85,61 +75,14 @@ __device__ int block_argmax(double bk, int bc, double* rk, int* rc) {
     return bc;
 }
 
-// Rules 2-4 with top_k > 0: every lane keeps its KM best allowed (ll, column) in registers, each wave pops its top_k best by butterfly
-// arg-max rounds, the NW x top_k wave winners are ranked in LDS, and one wave draws among the top-p survivors of the sorted list.
+// Rules 2-4 with top_k > 0: row_topk over the allowed columns, then one wave draws among the top-p survivors of the sorted list.
 template <int KM>
 __device__ int select_topk(const SampleArgs& a, const float* x, int b, uint64_t key) {
-    __shared__ float sv[NW][MAX_TOPK];
-    __shared__ int si[NW][MAX_TOPK];
     __shared__ float lv[MAX_TOPK];
     __shared__ int lc[MAX_TOPK];
     __shared__ int s_n;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, k = a.top_k;
-    float v[KM];
-    int ix[KM];
-#pragma unroll
-    for (int i = 0; i < KM; ++i) { v[i] = -INFINITY; ix[i] = INT_MAX; }
-    for (int c = threadIdx.x; c < a.tot; c += NT) {
-        const float y = x[c];
-        if (col_allowed(a, b, c, y) && before(y, c, v[KM - 1], ix[KM - 1])) {
-            v[KM - 1] = y; ix[KM - 1] = c;
-#pragma unroll
-            for (int i = KM - 1; i > 0; --i) {
-                if (before(v[i], ix[i], v[i - 1], ix[i - 1])) {
-                    const float tv = v[i]; v[i] = v[i - 1]; v[i - 1] = tv;
-                    const int ti = ix[i]; ix[i] = ix[i - 1]; ix[i - 1] = ti;
-                }
-            }
-        }
-    }
-    for (int r = 0; r < k; ++r) {
-        float bv = v[0];
-        int bi = ix[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(bi, o);
-            if (before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (ix[0] == bi) {              // the winning lane pops its head (sentinels: INT_MAX, -inf, never allowed columns)
-#pragma unroll
-            for (int i = 0; i < KM - 1; ++i) { v[i] = v[i + 1]; ix[i] = ix[i + 1]; }
-            v[KM - 1] = -INFINITY; ix[KM - 1] = INT_MAX;
-        }
-        if (lane == 0) { sv[w][r] = bv; si[w][r] = bi; }
-    }
-    if (threadIdx.x < MAX_TOPK) lc[threadIdx.x] = INT_MAX;
-    __syncthreads();
-    const int n = NW * k;
-    if (threadIdx.x < n) {
-        const int wi = threadIdx.x / k, ri = threadIdx.x % k;
-        const float y = sv[wi][ri];
-        const int yc = si[wi][ri];
-        int rank = 0;
-        for (int q = 0; q < n; ++q) rank += before(sv[q / k][q % k], si[q / k][q % k], y, yc);
-        if (rank < k && yc != INT_MAX) { lv[rank] = y; lc[rank] = yc; }
-    }
-    __syncthreads();
+    row_topk<KM>(x, a.tot, k, [&](int c, float y) { return col_allowed(a, b, c, y); }, lv, lc);
     if (threadIdx.x == 0) {
         int m = 0;
         while (m < k && lc[m] != INT_MAX) ++m;
@@ -207,16 +150,15 @@ __device__ int select_row(const SampleArgs& a, const float* x, int b, uint64_t k
     return bc == INT_MAX ? -1 : bc;
 }
 
-// One workgroup per slot.  active[3] rotates as in gtos_beam_advance: step t runs only if active[t % 3] is set (some slot was
-// sampling), ORs "this slot samples again" into active[(t + 1) % 3] and clears active[(t + 2) % 3] for step t + 1.  Every slot,
-// live or not, gets its next input (a dead slot the padding input).
+// One workgroup per slot.  The active[3] rotation of csrc/slot_kernels.h; the flag: does some slot sample again?  Every slot, live
+// or not, gets its next input (a dead slot the padding input).
 template <int KM>
 __global__ __launch_bounds__(NT) void sample_step_kernel(SampleArgs a) {
     __shared__ int s_run, s_next;
     const int s = blockIdx.x, b = s / a.k, j = s % a.k, t = a.t;
     if (threadIdx.x == 0) {
-        if (s == 0) a.active[(t + 2) % 3] = 0;
-        s_run = a.active[t % 3] && !a.state[(int64_t)s * SS_WORDS + SS_DEAD];
+        if (s == 0) a.active[active_clear(t)] = 0;
+        s_run = a.active[active_read(t)] && !a.state[(int64_t)s * SS_WORDS + SS_DEAD];
         s_next = -1;
     }
     __syncthreads();
@@ -228,22 +170,14 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(SampleArgs a) {
             const uint8_t f = w < 0 ? (uint8_t)TOK_PLAIN : token_flag(a.flag_shared, a.flag_local, a.V, a.tot, b, w);
             const bool on = update(s, t, a.max_t, w, w < 0 ? 0.0f : x[w], f, a.score, a.state, a.tokens + (int64_t)t * a.N);
             if (on) {
-                atomicOr(a.active + (t + 1) % 3, 1);
+                atomicOr(a.active + active_set(t), 1);
                 s_next = w;
             }
         }
         __syncthreads();
     }
     const int id = s_next;
-    const int64_t lid = (int64_t)b * (a.tot - a.V) + (id - a.V);
-    for (int c = (int)threadIdx.x - 1; c < a.C; c += NT) {             // c == -1: the token id
-        int64_t out;
-        if (id < 0) out = c < 0 ? a.dead_tok : a.dead_char[c];
-        else if (c < 0) out = id < a.V ? a.tok_shared[id] : a.tok_local[lid];
-        else out = id < a.V ? a.char_shared[(int64_t)id * a.C + c] : a.char_local[lid * a.C + c];
-        if (c < 0) a.tok_out[s] = out;
-        else a.char_out[(int64_t)s * a.C + c] = out;
-    }
+    for (int c = (int)threadIdx.x - 1; c < a.next.C; c += NT) write_next_input(a.next, a.V, a.tot, b, s, c, id);
 }
 
 }  // namespace
@@ -258,21 +192,18 @@ extern "C" int gtos_sample_step(int N, int k, int t, int V, int tot, int min_tim
     if (k < 1 || N % k || t < 0 || t >= max_time_step || V < 1 || tot < V || ld < tot || C < 1 || top_k < 0 || top_k > MAX_TOPK ||
         !(temperature > 0.0f && temperature < INFINITY) || !(top_p > 0.0f && top_p <= 1.0f))
         return -10;
-    if (!ll || !flag_shared || (tot > V && (!flag_local || !owned_local || !tok_local || !char_local)) || !score || !slot_state ||
-        !tokens || !active || !tok_shared || !char_shared || !dead_char || !tok_out || !char_out)
-        return -23;
     SampleArgs a{};
-    a.N = N; a.k = k; a.t = t; a.V = V; a.tot = tot; a.min_t = min_time_step; a.max_t = max_time_step; a.top_k = top_k; a.C = C;
+    a.next = NextInput{tok_shared, tok_local, char_shared, char_local, dead_tok, dead_char, C, tok_out, char_out};
+    if (!ll || !flag_shared || (tot > V && (!flag_local || !owned_local)) || !score || !slot_state || !tokens || !active ||
+        !next_input_ok(a.next, V, tot))
+        return -23;
+    a.N = N; a.k = k; a.t = t; a.V = V; a.tot = tot; a.min_t = min_time_step; a.max_t = max_time_step; a.top_k = top_k;
     a.T = (double)temperature; a.top_p = (double)top_p; a.seed = seed; a.ll = ll; a.ld = ld;
     a.flag_shared = flag_shared; a.flag_local = flag_local; a.owned_local = owned_local; a.score = score; a.state = slot_state;
-    a.tokens = tokens; a.active = active; a.tok_shared = tok_shared; a.tok_local = tok_local; a.char_shared = char_shared;
-    a.char_local = char_local; a.dead_tok = dead_tok; a.dead_char = dead_char; a.tok_out = tok_out; a.char_out = char_out;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 g((unsigned)N), blk(NT);
-    if (top_k <= 4) hipLaunchKernelGGL(sample_step_kernel<4>, g, blk, 0, s, a);
-    else if (top_k <= 8) hipLaunchKernelGGL(sample_step_kernel<8>, g, blk, 0, s, a);
-    else if (top_k <= 16) hipLaunchKernelGGL(sample_step_kernel<16>, g, blk, 0, s, a);
-    else hipLaunchKernelGGL(sample_step_kernel<32>, g, blk, 0, s, a);
+    a.tokens = tokens; a.active = active;
+    dispatch_km(top_k, [&](auto km) {
+        hipLaunchKernelGGL(sample_step_kernel<decltype(km)::value>, dim3((unsigned)N), dim3(NT), 0, static_cast<hipStream_t>(stream), a);
+    });
     GTOS_CHECK_LAUNCH();
     return 0;
 }

@@ -3,7 +3,7 @@
 // kernel runs the same helpers: the allowed set, the top-p cut of a sorted candidate list, the weights, the counter hash and the
 // Gumbel keys, and the slot update.
 //
-// Slots: B graphs x k samples, N = B*k; slot s is sample s % k of graph s / k.  One row = one live slot at step t:
+// Slots as in csrc/slot_kernels.h; slot s is sample s % k of graph s / k.  One row = one live slot at step t:
 //  1. allowed: columns c in [0, tot) with a finite ll, except <UNK> strings, copy ids c >= V the slot's graph does not own, and <END>
 //     while t < min_time_step;
 //  2. top-k (top_k > 0): the allowed columns ranked < top_k in (ll descending, column ascending) order;
@@ -14,18 +14,14 @@
 // A row with no allowed column stops its slot unfinished (no token).  Gumbel-max needs no sort and no fixed reduction order.
 #pragma once
 #include <math.h>
-#include <stdint.h>
 
-#if defined(__HIPCC__)
-#define GTOS_SAMPLE_HD __host__ __device__ inline
-#else
-#define GTOS_SAMPLE_HD inline
-#endif
+#include "slot_kernels.h"
+
+#define GTOS_SAMPLE_HD GTOS_SLOT_HD
 
 namespace gtos_sample {
 
-// string class of a token id, the tables of Generator.search_tables (the classes of gtos_beam)
-enum { TOK_PLAIN = 0, TOK_UNK = 1, TOK_END = 2 };
+using namespace gtos_slot;              // token classes, token_flag, before() (rule 2's order), the active[3] rotation
 // per-slot state words, int32 [N, SS_WORDS]: steps taken part in, completion step (<END>) or -1, dead (ended or stopped)
 enum { SS_STEPS = 0, SS_END = 1, SS_DEAD = 2, SS_WORDS = 3 };
 constexpr int MAX_TOPK = 32;
@@ -53,8 +49,6 @@ GTOS_SAMPLE_HD double draw_key(float ll, double T, uint64_t key, int c) { return
 // the top-p weight of a column, m the largest kept ll
 GTOS_SAMPLE_HD double weight(float ll, float m, double T) { return exp(((double)ll - (double)m) / T); }
 
-// (ll, column) a ranks before b: larger ll first, equal ll lower column first (the tie rule of gtos_beam_topk)
-GTOS_SAMPLE_HD bool before(float va, int ca, float vb, int cb) { return va > vb || (va == vb && ca < cb); }
 // draw key a beats b: larger key, equal keys lower column
 GTOS_SAMPLE_HD bool wins(double ka, int ca, double kb, int cb) { return ka > kb || (ka == kb && ca < cb); }
 
@@ -62,14 +56,8 @@ GTOS_SAMPLE_HD bool wins(double ka, int ca, double kb, int cb) { return ka > kb 
 GTOS_SAMPLE_HD bool allowed(const uint8_t* flag_shared, const uint8_t* flag_local, const uint8_t* owned_local, int V, int tot, int b,
                             int c, int t, int min_time_step, float ll) {
     if (!(ll > -INFINITY && ll < INFINITY)) return false;              // -inf, +inf and NaN are never drawn
-    uint8_t f;
-    if (c < V) {
-        f = flag_shared[c];
-    } else {
-        const int64_t l = (int64_t)b * (tot - V) + (c - V);
-        if (!owned_local[l]) return false;
-        f = flag_local[l];
-    }
+    if (c >= V && !owned_local[local_index(V, tot, b, c)]) return false;
+    const uint8_t f = token_flag(flag_shared, flag_local, V, tot, b, c);
     return f == TOK_PLAIN || (f == TOK_END && t >= min_time_step);
 }
 
@@ -179,11 +167,6 @@ GTOS_SAMPLE_HD bool update(int s, int t, int max_time_step, int w, float ll_w, u
         return false;
     }
     return t + 1 < max_time_step;
-}
-
-// class of an output id (the slot's graph b; ids >= V from its copy table)
-GTOS_SAMPLE_HD uint8_t token_flag(const uint8_t* flag_shared, const uint8_t* flag_local, int V, int tot, int b, int id) {
-    return id < V ? flag_shared[id] : flag_local[(int64_t)b * (tot - V) + (id - V)];
 }
 
 }  // namespace gtos_sample

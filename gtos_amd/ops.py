@@ -1340,14 +1340,28 @@ def beam_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, flag_sh
          ptr(active), stream())
 
 
+def _check_next_input(N, k, V, tot, tok_shared, tok_local, char_shared, char_local, dead_char, tok_out, char_out):
+    """The next-input table group of beam_reorder / sample_step (NextInput in csrc/slot_device.h): int64, contiguous, sized for N
+    slots of k per graph, ids [0, V) shared and [V, tot) per graph, C characters.  -> C"""
+    C = char_out.shape[-1]
+    require_cuda(tok_shared, char_shared, dead_char, tok_out, char_out)
+    for x in (tok_shared, char_shared, dead_char, tok_out, char_out, tok_local, char_local):
+        assert x is None or (x.dtype == torch.int64 and x.is_contiguous())
+    assert tok_out.numel() == N and char_out.numel() == N * C and dead_char.numel() == C and char_shared.shape[-1] == C
+    assert tok_shared.numel() >= V and char_shared.numel() >= V * C
+    if tot > V:
+        assert tok_local.numel() >= N // k * (tot - V) and char_local.numel() >= N // k * (tot - V) * C
+    return C
+
+
 def beam_reorder(src, dst, t, k, bp_parent, bp_token, beam_state, active, V, tot, tok_shared, tok_local, char_shared, char_local,
                  dead_tok, dead_char, tok_out, char_out):
     """After the advance of step t: rows [0,t] of every cache src[i] ([T_max, N, w], contiguous) gathered by parent slot into dst[i],
     and the next input (tok_out [N] int64, char_out [N,C] int64) of every slot (gtos_beam_reorder)."""
     import ctypes
     T_max, N = bp_parent.shape
-    C = char_out.shape[-1]
-    require_cuda(bp_parent, bp_token, beam_state, active, tok_shared, char_shared, dead_char, tok_out, char_out, *src, *dst)
+    C = _check_next_input(N, k, V, tot, tok_shared, tok_local, char_shared, char_local, dead_char, tok_out, char_out)
+    require_cuda(bp_parent, bp_token, beam_state, active, *src, *dst)
     row_bytes = 0
     for a, b in zip(src, dst):
         assert a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous()
@@ -1356,13 +1370,6 @@ def beam_reorder(src, dst, t, k, bp_parent, bp_token, beam_state, active, V, tot
         assert row_bytes in (0, rb), "beam_reorder: every cache must have the same row width"
         row_bytes = rb
     assert len(src) == len(dst) and (len(src) == 0 or row_bytes > 0)
-    for x in (tok_shared, char_shared, dead_char, tok_out, char_out, tok_local, char_local):
-        assert x is None or (x.dtype == torch.int64 and x.is_contiguous())
-    assert tok_out.numel() == N and char_out.numel() == N * C and dead_char.numel() == C and char_shared.shape[-1] == C
-    assert tok_shared.numel() >= V and char_shared.numel() >= V * C
-    if tot > V:
-        B = N // k
-        assert tok_local.numel() >= B * (tot - V) and char_local.numel() >= B * (tot - V) * C
     n = len(src)
     S = (ctypes.c_void_p * max(1, n))(*[x.data_ptr() for x in src])
     D = (ctypes.c_void_p * max(1, n))(*[x.data_ptr() for x in dst])
@@ -1378,23 +1385,16 @@ def sample_step(t, k, V, tot, min_time_step, max_time_step, temperature, top_k, 
                 char_out):
     """One sampling step of every slot at step t (gtos_sample_step): draws from ll [N, tot] fp32, updates score, slot_state, row t of
     tokens and active in place, and writes the next input (tok_out [N] int64, char_out [N,C] int64)."""
-    require_cuda(ll, flag_shared, score, slot_state, tokens, active, tok_shared, char_shared, dead_char, tok_out, char_out)
+    require_cuda(ll, flag_shared, score, slot_state, tokens, active)
     N = slot_state.shape[0]
-    C = char_out.shape[-1]
+    C = _check_next_input(N, k, V, tot, tok_shared, tok_local, char_shared, char_local, dead_char, tok_out, char_out)
     if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1 or ll.shape != (N, tot):
         raise _lib.GtosHipError("sample_step: ll must be an [N, tot] fp32 tensor with unit column stride")
     assert slot_state.shape == (N, 3) and slot_state.dtype == torch.int32 and score.dtype == torch.float64 and score.numel() == N
     assert tokens.shape == (max_time_step, N) and tokens.dtype == torch.int32 and active.numel() == 3 and active.dtype == torch.int32
     assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
-    if tot > V:
-        B = N // k
-        for x in (flag_local, owned_local):
-            assert x is not None and x.dtype == torch.uint8 and x.numel() >= B * (tot - V)
-        assert tok_local.numel() >= B * (tot - V) and char_local.numel() >= B * (tot - V) * C
-    for x in (tok_shared, char_shared, dead_char, tok_out, char_out, tok_local, char_local):
-        assert x is None or (x.dtype == torch.int64 and x.is_contiguous())
-    assert tok_out.numel() == N and char_out.numel() == N * C and dead_char.numel() == C and char_shared.shape[-1] == C
-    assert tok_shared.numel() >= V and char_shared.numel() >= V * C
+    for x in (flag_local, owned_local) if tot > V else ():
+        assert x is not None and x.dtype == torch.uint8 and x.numel() >= N // k * (tot - V)
     for x in (flag_shared, flag_local, owned_local, score, slot_state, tokens, active):
         assert x is None or x.is_contiguous()
     call("gtos_sample_step", N, k, t, V, tot, min_time_step, max_time_step, float(temperature), top_k, float(top_p),

@@ -19,6 +19,9 @@ flag every ``sync_every`` steps and the back-pointer / completion tables once at
 ``sample_device`` decodes by sampling instead (csrc/sample.hip): the same fixed slots, one independent sample per slot with
 temperature / top-k / top-p, and Beam objects filled the same way.
 """
+import math
+import types
+
 import torch
 
 from . import ops
@@ -115,21 +118,43 @@ def beam_search(model, beams, memory):
     return beams
 
 
-def beam_search_device(model, memory, beams, sync_every=8, stats=None):
-    """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
-    decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
-    steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
-    keep computing on the padding input and zero cache rows, their candidates are ignored.  The loop reads the device's "some
-    not-done beam has a live slot" flag every ``sync_every`` steps (steps past the end are no-ops); at the end the tables are read
-    once and the Beam objects filled as beam_search leaves them (hypotheses, completed_hypotheses in append order, steps).
-    ``stats`` (a dict, optional) receives the decoder steps launched and the host reads made."""
+def _arena(dtype, cuts, dev):
+    """One zeroed allocation cut into named views, so that the host reads all of them with one copy.  ``cuts``: (name, shape, init),
+    init a number, or a tuple that every row of the last axis starts as.  -> ({name: view}, read), read() -> {name: flat list}."""
+    sizes = [math.prod(shape) for _, shape, _ in cuts]
+    flat = torch.zeros(sum(sizes), dtype=dtype, device=dev)
+    views = {}
+    for (name, shape, init), part in zip(cuts, torch.split(flat, sizes)):
+        views[name] = part.view(shape)
+        if isinstance(init, tuple):
+            for j, x in enumerate(init):
+                if x:
+                    views[name][..., j] = x
+        elif init:
+            views[name].fill_(init)
+    return views, lambda: {cut[0]: part.tolist() for cut, part in zip(cuts, torch.split(flat.cpu(), sizes))}
+
+
+def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, layout, step, fill):
+    """The fixed-slot decode loop (the contract of csrc/slot_kernels.h) behind ``who``, a public function: B graphs x k slots, N = B*k,
+    slot s belongs to graph s // k, the graph memory gathered per slot once, every slot decoded every step (a dead slot on the
+    padding input), the input of step t + 1 written by step t's kernels into the other of two buffers.  The loop reads the device's
+    continue flag ``active`` every ``sync_every`` steps (steps past the end are no-ops) and the tables once at the end, one copy per
+    arena; ``stats`` (a dict, optional) receives the decoder steps launched and the host reads made.  A decoder supplies
+      copies: buffers per self-attention cache (Generator.slot_caches), 2 when step() reorders one into the other;
+      live0: slots per graph that start on <STR>, the rest on the padding input (None: all k);
+      layout(d) -> (int32 cuts, fp64 cuts) of its tables, as _arena takes them (also the place to hang tables of its own on d);
+        d holds B, k, N, min_t, max_t, V, tot, local, tab (Generator.search_tables) and then arr, the views by name with ``active``;
+      step(d, t, ll, cur, nxt, tok_out, char_out): step t's launches after the decoder's, ll [N, tot] fp32; cur / nxt: the caches
+        read and those step t + 1 reads (the same with one copy); tok_out [N] / char_out [N,C]: step t + 1's input, for EVERY slot;
+      fill(beams, k, token_string=, **tables) -> the Beam objects from its tables as flat lists; token_string(b, id) -> the string."""
     B = len(beams)
     if not B:
         return beams
     k, min_t, max_t = beams[0].beam_size, beams[0].min_time_step, beams[0].max_time_step
     for beam in beams:
         assert (beam.beam_size, beam.min_time_step, beam.max_time_step) == (k, min_t, max_t), "beams of one search share their settings"
-        assert beam.steps == 0 and len(beam.hypotheses) == 1 and not beam.completed_hypotheses, "beam_search_device takes fresh beams"
+        assert beam.steps == 0 and len(beam.hypotheses) == 1 and not beam.completed_hypotheses, who + " takes fresh beams"
     n_steps, reads = 0, 0
     if max_t <= 0:                                          # every beam is complete before the first step
         if stats is not None:
@@ -143,49 +168,54 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None):
     tot = max(int(memory['tot_ext']), V)
     tab = model.search_tables(local, tot)
     C = tab['C']
-    # one int32 and one fp64 arena, so that the final read is two copies
-    ints = torch.empty(3 + 4 * B + 2 * max_t * N + 2 * B * k, dtype=torch.int32, device=dev)
-    cuts = [3, 4 * B, max_t * N, max_t * N, B * k, B * k]
-    active, state, bp_parent, bp_token, comp_step, comp_parent = torch.split(ints, cuts)
-    state, bp_parent, bp_token = state.view(B, 4), bp_parent.view(max_t, N), bp_token.view(max_t, N)
-    comp_step, comp_parent = comp_step.view(B, k), comp_parent.view(B, k)
-    active.zero_()
-    active[0] = 1
-    state.zero_()
-    state[:, 2] = 1                                         # one live hypothesis (<STR>) per beam
-    bp_parent.fill_(-1)
-    bp_token.fill_(-1)
-    comp_step.zero_()
-    comp_parent.zero_()
-    dbl = torch.zeros(N + B * k, dtype=torch.float64, device=dev)
-    slot_score, comp_score = dbl[:N], dbl[N:].view(B, k)
-    caches = model.slot_caches(max_t, N)
+    d = types.SimpleNamespace(B=B, k=k, N=N, min_t=min_t, max_t=max_t, V=V, tot=tot, local=local, tab=tab)
+    int_cuts, dbl_cuts = layout(d)
+    ints, read_ints = _arena(torch.int32, [('active', (3,), (1, 0, 0))] + int_cuts, dev)
+    dbls, read_dbls = _arena(torch.float64, dbl_cuts, dev)
+    d.arr = dict(ints, **dbls)
+    caches = model.slot_caches(max_t, N, copies=copies)
+    caches = [[c[i] for c in caches] for i in range(copies)]
     tok = [torch.full((1, N), tab['dead_tok'], dtype=torch.int64, device=dev) for _ in range(2)]
     chars = [tab['dead_char'].expand(1, N, C).contiguous() for _ in range(2)]
-    tok[0][0, ::k] = tab['start_tok']
-    chars[0][0, ::k] = tab['start_char']
+    tok[0].view(B, k)[:, :live0] = tab['start_tok']
+    chars[0].view(B, k, C)[:, :live0] = tab['start_char']
     for t in range(max_t):
         cur, nxt = t % 2, (t + 1) % 2
-        ll = model.decode_slots((tok[cur], chars[cur]), [c[cur] for c in caches], mem, t)
-        topv, topi = ops.beam_topk(ll, k)
-        ops.beam_advance(t, k, V, tot, min_t, max_t, topv, topi, tab['flag_shared'], tab['flag_local'], slot_score, state,
-                         bp_parent, bp_token, comp_step, comp_parent, comp_score, active)
-        ops.beam_reorder([c[cur] for c in caches], [c[nxt] for c in caches], t, k, bp_parent, bp_token, state, active, V, tot,
-                         tab['tok_shared'], tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'],
-                         tab['dead_char'], tok[nxt][0], chars[nxt][0])
+        ll = model.decode_slots((tok[cur], chars[cur]), caches[cur % copies], mem, t)
+        step(d, t, ll, caches[cur % copies], caches[nxt % copies], tok[nxt][0], chars[nxt][0])
         n_steps += 1
         if (t + 1) % sync_every == 0 and t + 1 < max_t:
             reads += 1
-            if not int(active[(t + 1) % 3].item()):
+            if not int(ints['active'][(t + 1) % 3].item()):
                 break
-    ints_h, dbl_h = ints.cpu(), dbl.cpu()
+    host = dict(read_ints(), **read_dbls())
+    del host['active']
     reads += 2
     if stats is not None:
         stats.update(steps=n_steps, host_reads=reads)
-    _, state, bp_parent, bp_token, comp_step, comp_parent = [x.tolist() for x in torch.split(ints_h, cuts)]
     pv = model.vocabs['predictable_token']
-    return fill_beams(beams, k, state, bp_parent, bp_token, comp_step, comp_parent, dbl_h[:N].tolist(), dbl_h[N:].tolist(),
-                      lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i))
+    return fill(beams, k, token_string=lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i), **host)
+
+
+def beam_search_device(model, memory, beams, sync_every=8, stats=None):
+    """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
+    decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
+    steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
+    keep computing on the padding input and zero cache rows, their candidates are ignored.  The continue flag is "some not-done
+    beam has a live slot"; ``sync_every`` and ``stats`` as in _slot_decode.  The Beam objects are filled as beam_search leaves them
+    (hypotheses, completed_hypotheses in append order, steps)."""
+    def layout(d):
+        return ([('state', (d.B, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
+                 ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0)], [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0)])
+
+    def step(d, t, ll, cur, nxt, tok_out, char_out):
+        a, tab = d.arr, d.tab
+        topv, topi = ops.beam_topk(ll, d.k)
+        ops.beam_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, topv, topi, tab['flag_shared'], tab['flag_local'], a['slot_score'],
+                         a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'], a['active'])
+        ops.beam_reorder(cur, nxt, t, d.k, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
+                         tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+    return _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill_beams)
 
 
 def slot_memory(memory, B, k):
@@ -239,62 +269,19 @@ def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_ev
     gets ``beam_size`` independent samples in fixed slots (slot s is sample s % k of graph s // k), each drawing its next token by the
     rule of csrc/sample_kernels.h (temperature, top_k, top_p; <UNK>, other graphs' copy ids and <END> before min_time_step are never
     drawn) from a counter hash of (seed, graph, sample, step, column).  A sample never changes parent, so each layer keeps ONE
-    [max_time_step, N, 2d] cache and nothing is reordered.  The host reads the continue flag every ``sync_every`` steps and the
-    tables once at the end.  Returns the beams filled like a beam search's: completed_hypotheses (ended by <END>) by completion step,
-    then sample index; hypotheses (unfinished) in sample order; score = the fp64 sum of the model's ll of the drawn tokens.
-    ``stats`` (a dict, optional) receives the decoder steps launched and the host reads made."""
-    B = len(beams)
-    if not B:
-        return beams
-    k, min_t, max_t = beams[0].beam_size, beams[0].min_time_step, beams[0].max_time_step
-    for beam in beams:
-        assert (beam.beam_size, beam.min_time_step, beam.max_time_step) == (k, min_t, max_t), "beams of one search share their settings"
-        assert beam.steps == 0 and len(beam.hypotheses) == 1 and not beam.completed_hypotheses, "sample_device takes fresh beams"
-    n_steps, reads = 0, 0
-    if max_t <= 0:
-        if stats is not None:
-            stats.update(steps=0, host_reads=0)
-        return beams
-    dev = memory['probe'].device
-    N = B * k
-    mem = slot_memory(memory, B, k)
-    local = memory['local_idx2token']
-    V = model.vocabs['predictable_token'].size
-    tot = max(int(memory['tot_ext']), V)
-    tab = model.search_tables(local, tot)
-    owned = model.sample_tables(local, tot)
-    C = tab['C']
-    ints = torch.empty(3 + 3 * N + max_t * N, dtype=torch.int32, device=dev)
-    cuts = [3, 3 * N, max_t * N]
-    active, state, tokens = torch.split(ints, cuts)
-    state, tokens = state.view(N, 3), tokens.view(max_t, N)
-    active.zero_()
-    active[0] = 1
-    state.zero_()
-    state[:, 1] = -1                                        # no completion yet
-    tokens.fill_(-1)
-    score = torch.zeros(N, dtype=torch.float64, device=dev)
-    caches = [c[0] for c in model.slot_caches(max_t, N, copies=1)]
-    tok = [torch.full((1, N), tab['start_tok'], dtype=torch.int64, device=dev) for _ in range(2)]
-    chars = [tab['start_char'].expand(1, N, C).contiguous() for _ in range(2)]
-    for t in range(max_t):
-        cur, nxt = t % 2, (t + 1) % 2
-        ll = model.decode_slots((tok[cur], chars[cur]), caches, mem, t)
-        ops.sample_step(t, k, V, tot, min_t, max_t, temperature, top_k, top_p, seed, ll, tab['flag_shared'], tab['flag_local'], owned,
-                        score, state, tokens, active, tab['tok_shared'], tab['tok_local'], tab['char_shared'], tab['char_local'],
-                        tab['dead_tok'], tab['dead_char'], tok[nxt][0], chars[nxt][0])
-        n_steps += 1
-        if (t + 1) % sync_every == 0 and t + 1 < max_t:
-            reads += 1
-            if not int(active[(t + 1) % 3].item()):
-                break
-    ints_h, score_h = ints.cpu(), score.cpu()
-    reads += 2
-    if stats is not None:
-        stats.update(steps=n_steps, host_reads=reads)
-    _, state, tokens = [x.tolist() for x in torch.split(ints_h, cuts)]
-    pv = model.vocabs['predictable_token']
-    return fill_samples(beams, k, state, tokens, score_h.tolist(), lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i))
+    [max_time_step, N, 2d] cache and nothing is reordered; ``sync_every`` and ``stats`` as in _slot_decode.  Returns the beams filled
+    like a beam search's: completed_hypotheses (ended by <END>) by completion step, then sample index; hypotheses (unfinished) in
+    sample order; score = the fp64 sum of the model's ll of the drawn tokens."""
+    def layout(d):
+        d.owned = model.sample_tables(d.local, d.tot)
+        return [('state', (d.N, 3), (0, -1, 0)), ('tokens', (d.max_t, d.N), -1)], [('score', (d.N,), 0)]      # -1: no completion yet
+
+    def step(d, t, ll, cur, nxt, tok_out, char_out):
+        a, tab = d.arr, d.tab
+        ops.sample_step(t, d.k, d.V, d.tot, d.min_t, d.max_t, temperature, top_k, top_p, seed, ll, tab['flag_shared'], tab['flag_local'],
+                        d.owned, a['score'], a['state'], a['tokens'], a['active'], tab['tok_shared'], tab['tok_local'],
+                        tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+    return _slot_decode("sample_device", model, memory, beams, sync_every, stats, 1, None, layout, step, fill_samples)
 
 
 def fill_samples(beams, k, state, tokens, score, token_string):

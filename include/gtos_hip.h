@@ -413,7 +413,7 @@ int gtos_copy_nll_ls_bwd(int dtype, int T, int B, int V, int S, const void* logi
  * Operands as gtos_copy_nll_fwd.  SHAPES (-24 outside): V >= 1, 0 <= S <= 4096, ld_logits >= V; -23 for a null pointer.
  * _copy_eval_fwd: nll[t,b] fp32, bitwise what gtos_copy_nll_fwd writes (0 where target == pad_idx); pred[t,b] int32 = argmax_k of the
  *   mixture p_k = gen_gate * softmax(logits)_k [k < V] + copy_gate * sum_{s: cp_seq[s,b] == k} align[t,b,s], equal values to the lower
- *   column (the rule of gtos_beam_topk), and p_pred[t,b] fp32 = that maximum.  A padded row still gets its pred / p_pred.
+ *   column (the order of csrc/slot_kernels.h), and p_pred[t,b] fp32 = that maximum.  A padded row still gets its pred / p_pred.
  * _eval_accumulate (one workgroup, fixed summation order): per column b the fp64 sum of nll[:, b] over the non-pad targets in t order,
  *   their count and the count of pred == target among them into sent_nll fp64 [B], sent_tokens / sent_correct int32 [B]; and ADDS to
  *   totals fp64 [5] = (sum nll, tokens, correct, sentences, sum_b sent_nll[b] / sent_tokens[b]) over the columns in column order.  The
@@ -426,7 +426,9 @@ int gtos_eval_accumulate(int T, int B, const float* nll, const int* pred, const 
 
 /* ---- Device-resident beam search (csrc/beam.hip; selection rule in csrc/beam_kernels.h), driven by
  * gtos_amd.search.beam_search_device: generator/search.py's Beam.update / Beam.completed / search_by_batch without a host round trip
- * per step.  B sentences x k fixed hypothesis slots, N = B*k, slot s belongs to sentence s / k.  SHAPES (-10 outside): k <= 32.
+ * per step.  B sentences x k fixed hypothesis slots, N = B*k, slot s belongs to sentence s / k; the slots, the token classes, the
+ * (ll, column) order, the active flag and the next-input tables are those of csrc/slot_kernels.h and csrc/slot_device.h, which
+ * gtos_sample_step shares.  SHAPES (-10 outside): k <= 32.
  * _topk: per row of ll [rows, tot] fp32 (row stride ld >= tot >= k), the k largest values val [rows,k] and their columns
  *   idx int32 [rows,k], descending, equal values lower column first (the torch.topk of generator.py:163).
  * _advance (one workgroup per sentence, step t < max_time_step): pools the candidates (topv / topi [N,k]) of the sentence's live slots
@@ -462,9 +464,10 @@ int gtos_beam_reorder(int n_caches, void* const* src, void* const* dst, int64_t 
  *   then to the smallest ll threshold whose set holds a top_p share of sum exp((ll - max) / temperature) (fp64; ties kept), and
  *   picked by Gumbel-max, argmax ll / temperature + g with g from a splitmix64 hash of (seed, s / k, s % k, t, column).  It adds
  *   ll[winner] to score fp64 [N], writes the winner to row t of tokens int32 [max_time_step, N] and updates slot_state int32 [N,3] =
- *   steps, completion step (<END>) or -1, dead; a row with nothing allowed stops its slot unfinished.  Token classes as in _advance.
- *   active int32 [3] rotates like _advance's: step t runs only if active[t % 3] is set.  Every slot's next input goes to tok_out
- *   int64 [N] / char_out int64 [N,C] from the tables of _reorder (dead or finished slots: dead_tok / dead_char).  There is no cache
+ *   steps, completion step (<END>) or -1, dead; a row with nothing allowed stops its slot unfinished.  Token classes (flag_shared /
+ *   flag_local) and the active int32 [3] rotation are those of csrc/slot_kernels.h: step t runs only if active[t % 3] is set.
+ *   Every slot's next input goes to tok_out int64 [N] / char_out int64 [N,C] from the NextInput tables of csrc/slot_device.h
+ *   (tok_* / char_* shared and local; dead or finished slots: dead_tok / dead_char).  There is no cache
  *   reorder: a sample's parent is itself. */
 int gtos_sample_step(int N, int k, int t, int V, int tot, int min_time_step, int max_time_step, float temperature, int top_k,
                      float top_p, uint64_t seed, const float* ll, int64_t ld, const uint8_t* flag_shared,

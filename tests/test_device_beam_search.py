@@ -5,15 +5,13 @@ CPU: the selection header compiled with g++ is driven through random multi-step 
 must agree exactly.  GPU: the three kernels against torch / Beam.advance, and Generator.work(search="device") against the reference's
 beams and against the host search."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_DIR = os.path.join(ROOT, "gtos_amd", "csrc")
+from tests_support import compile_host_driver
+
 
 DRIVER = r"""
 #include "beam_kernels.h"
@@ -26,12 +24,12 @@ extern "C" void advance_all(int B, int k, int t, int V, int tot, int min_t, int 
     static int pt[MAX_K * MAX_K], order[MAX_K];
     static uint8_t pf[MAX_K * MAX_K];
     const long N = (long)B * k;
-    active[(t + 2) % 3] = 0;
-    if (!active[t % 3]) return;
+    active[active_clear(t)] = 0;
+    if (!active[active_read(t)]) return;
     for (int b = 0; b < B; ++b)
         if (advance_serial(b, k, t, V, tot, min_t, max_t, topv, topi, fs, fl, slot_score, state, bp_parent + t * N, bp_token + t * N,
                            comp_step, comp_parent, comp_score, ps, pt, pf, order))
-            active[(t + 1) % 3] |= 1;
+            active[active_set(t)] |= 1;
 }
 """
 
@@ -40,12 +38,7 @@ PAD, UNK, STR, END = "<PAD>", "<UNK>", "<STR>", "<END>"
 
 @pytest.fixture(scope="module")
 def host_advance(tmp_path_factory):
-    d = tmp_path_factory.mktemp("beam_host")
-    src, lib = d / "driver.cpp", d / "libbeam_host.so"
-    src.write_text(DRIVER)
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC",
-                           "-I", HEADER_DIR, str(src), "-o", str(lib)])
-    fn = ctypes.CDLL(str(lib)).advance_all
+    fn = compile_host_driver(tmp_path_factory, "beam_host", DRIVER).advance_all
     fn.argtypes = [ctypes.c_int] * 7 + [ctypes.c_void_p] * 12
     fn.restype = None
     return fn

@@ -10,15 +10,13 @@ float64 torch autograd inside NaN guard bands, eps = 0 bitwise at the op and to 
 oracle with the loss formed from its differentiable ll row, and a captured graph replayed on a batch with another C."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_DIR = os.path.join(ROOT, "gtos_amd", "csrc")
+from tests_support import compile_host_driver
+
 
 DRIVER = r"""
 #include "copy_ls_kernels.h"
@@ -37,12 +35,7 @@ PAD = 0
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("ls_host")
-    src, lib = d / "driver.cpp", d / "libls_host.so"
-    src.write_text(DRIVER)
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC",
-                           "-I", HEADER_DIR, str(src), "-o", str(lib)])
-    so = ctypes.CDLL(str(lib))
+    so = compile_host_driver(tmp_path_factory, "ls_host", DRIVER)
     P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
     so.ws_words.argtypes, so.ws_words.restype = [I, I, I], ctypes.c_longlong
     so.build.argtypes, so.build.restype = [P, I, I, I, P], None

@@ -6,15 +6,13 @@ Python restatement, and Generator.work's argument checks.  GPU: gtos_sample_step
 state words, token table, next input), the sampled distribution against softmax(ll / T) on the kept set, and end to end on C1 (fp32)
 and C2 (bf16) models: greedy equality with a host loop, seeds, sync_every, vocabulary invariants and teacher-forced scores."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_DIR = os.path.join(ROOT, "gtos_amd", "csrc")
+from tests_support import compile_host_driver
+
 
 DRIVER = r"""
 #include "sample_kernels.h"
@@ -38,12 +36,7 @@ GRID = [(T, k, p) for T in (0.3, 1.0, 2.5) for k in (0, 1, 5, 32) for p in (0.3,
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("sample_host")
-    src, lib = d / "driver.cpp", d / "libsample_host.so"
-    src.write_text(DRIVER)
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC",
-                           "-I", HEADER_DIR, str(src), "-o", str(lib)])
-    so = ctypes.CDLL(str(lib))
+    so = compile_host_driver(tmp_path_factory, "sample_host", DRIVER)
     so.select_row.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_double,
                               ctypes.c_uint64]

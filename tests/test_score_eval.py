@@ -18,14 +18,13 @@ On the GPU nll is held to test_label_smoothing.within() as the kernels of the sm
 import ctypes
 import os
 import socket
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER_DIR = os.path.join(ROOT, "gtos_amd", "csrc")
+from tests_support import compile_host_driver
+
 PAD = 0
 NEAR = 1e-5
 NEAR_SHARE = 0.01
@@ -41,12 +40,7 @@ extern "C" void row(const float* x, int V, float d0, float d1, const float* a, i
 
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("eval_host")
-    src, lib = d / "driver.cpp", d / "libeval_host.so"
-    src.write_text(DRIVER)
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC",
-                           "-I", HEADER_DIR, str(src), "-o", str(lib)])
-    so = ctypes.CDLL(str(lib))
+    so = compile_host_driver(tmp_path_factory, "eval_host", DRIVER)
     P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
     so.row.argtypes, so.row.restype = [P, I, F, F, P, I, P, I, I, L, L, P, P, P], None
     return so

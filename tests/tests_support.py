@@ -1,8 +1,24 @@
-"""Shared constants (must match tests/golden/make_golden.py) and helpers of the GPU tests."""
+"""Shared constants (must match tests/golden/make_golden.py) and helpers of the tests."""
+import ctypes
+import os
+import subprocess
+
 import torch
 
 SMALL_VOCAB = dict(concept=60, token=70, predictable_token=50, relation=26, concept_char=20, token_char=22)
 SMALL_GEN_ARGS = (8, 12, 8, 12, [(3, 16)], 10, 10, 6, 8, 2)   # char/word dims, filters, rel_dim, rnn
+
+
+def compile_host_driver(tmp_path_factory, name, source):
+    """``source`` (C++ that includes rule headers of gtos_amd/csrc and exports extern "C" functions) compiled with $CXX (g++) as the
+    kernels' exact-FP objects are (no contraction) -> the loaded ctypes.CDLL.  ``name``: of the temporary directory and the library."""
+    d = tmp_path_factory.mktemp(name)
+    src, lib = d / "driver.cpp", d / ("lib%s.so" % name)
+    src.write_text(source)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC",
+                           "-I", os.path.join(root, "gtos_amd", "csrc"), str(src), "-o", str(lib)])
+    return ctypes.CDLL(str(lib))
 
 
 def full_model_pair(dev, cfg_name, B, layers=None):
