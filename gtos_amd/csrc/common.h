@@ -84,6 +84,7 @@ __device__ __forceinline__ uint64_t live_seed(uint64_t seed) {
     }
 extern "C" __attribute__((visibility("hidden"))) int gtosi_gemm_set_seed_epoch(const void* p);
 extern "C" __attribute__((visibility("hidden"))) int gtosi_rel_attn_set_seed_epoch(const void* p);
+extern "C" __attribute__((visibility("hidden"))) int gtosi_attn_tile_set_seed_epoch(const void* p);
 extern "C" __attribute__((visibility("hidden"))) int gtosi_rowops_set_seed_epoch(const void* p);
 extern "C" __attribute__((visibility("hidden"))) int gtosi_gru_step_set_seed_epoch(const void* p);
 extern "C" __attribute__((visibility("hidden"))) int gtosi_tokenenc_set_seed_epoch(const void* p);

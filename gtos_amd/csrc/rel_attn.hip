@@ -32,7 +32,13 @@
 // the GENERIC lane map: a head takes LH = pow2ceil(hd/8) lanes (the lanes past hd/8 idle), a key row takes nhs heads =
 // LR = nhs*LH <= 64 lanes, and the heads are processed in ceil(H/nhs) independent SLICES (blockIdx.y) -- attention heads
 // never mix, so a slice is the same kernel on its own channels.  Same arithmetic, same dropout counters.
+//
+// Mode 0 in bf16 on the fast lane map with T >= 16 and hd in {32, 64, 128} does not run here: gtos_rel_attn_fwd / _bwd hand it to the
+// MFMA tile kernels of attn_tile.hip (GTOS_ATTN_TILE=0 keeps it here).  Everything else -- fp32, modes 1 and 2, the generic lane map, the
+// T = 1 decode step, other head widths (the hd = 512 alignment layer), a backward with an upstream gradient on a shape the tile path
+// does not cover -- runs on the streaming kernels below, unchanged.
 #include "common.h"
+#include "attn_tile.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -686,6 +692,15 @@ static int fill_args(AttnArgs& a, Geo& g, int T_, int S, int B, int H, int d, in
     return 0;
 }
 
+static AttnTileArgs tile_args(const AttnArgs& a) {
+    AttnTileArgs t = {};
+    t.q = a.q; t.k = a.k; t.v = a.v; t.ldq = a.ldq; t.ldk = a.ldk; t.ldv = a.ldv; t.key_pad = a.key_pad; t.attn_mask = a.attn_mask;
+    t.o = a.o; t.ldo = a.ldo; t.lse = a.lse; t.w = a.w; t.d_o = a.d_o; t.lddo = a.lddo; t.dw = a.dw;
+    t.dq = a.dq; t.dk = a.dk; t.dv = a.dv; t.lddq = a.lddq; t.lddk = a.lddk; t.lddv = a.lddv;
+    t.T = a.T; t.S = a.S; t.B = a.B; t.H = a.H; t.d = a.d; t.scale = a.scale; t.p_drop = a.p_drop; t.seed = a.seed;
+    return t;
+}
+
 extern "C" int gtos_rel_attn_fwd(int dtype, int mode, int T_, int S, int B, int H, int d,
                                  const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                  const void* rel, const int* idx_q, const uint8_t* key_pad, const uint8_t* attn_mask,
@@ -697,6 +712,10 @@ extern "C" int gtos_rel_attn_fwd(int dtype, int mode, int T_, int S, int B, int 
     if (rc) return rc;
     a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.rel = rel; a.idx_q = idx_q;
     a.key_pad = key_pad; a.attn_mask = attn_mask; a.o = o; a.ldo = ldo; a.lse = lse; a.w = w;
+    if (mode == 0 && dtype == GTOS_BF16 && !geo.generic) {
+        const AttnTileArgs t = tile_args(a);
+        if (gtosi_attn_tile_covers(T_, S, B, H, d, t, false)) return gtosi_attn_tile_fwd(t, stream);
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid(nblocks(T_, B), geo.slices);
     return dispatch_lh(geo.LH, [&](auto lh) {
@@ -732,6 +751,11 @@ extern "C" int gtos_rel_attn_bwd(int dtype, int mode, int T_, int S, int B, int 
     a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv; a.d_rel = d_rel; a.ld_drel = ld_drel; a.pd = pd; a.gs = gs;
     if (mode == 2 && d_rel && (ld_drel < 2 * d || ld_drel % 8)) return -14;
     if (dw && !w) return -13;
+    if (mode == 0 && dtype == GTOS_BF16 && !geo.generic) {
+        const AttnTileArgs t = tile_args(a);
+        if (gtosi_attn_tile_covers(T_, S, B, H, d, t, true)) return gtosi_attn_tile_bwd(t, stream);
+    }
+    if (!pd || !gs) return -15;               // the streaming passes hand P~ and scale*dS over through these
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 gq(nblocks(T_, B), geo.slices), gk(nblocks(S, B), geo.slices);
     return dispatch_lh(geo.LH, [&](auto lh) {

@@ -1234,6 +1234,7 @@ extern "C" int gtos_transpose_batch_bf16(int n_mat, const int64_t* desc, const i
 extern "C" int gtos_set_seed_epoch(const void* epoch) {
     int rc = gtosi_gemm_set_seed_epoch(epoch);
     if (!rc) rc = gtosi_rel_attn_set_seed_epoch(epoch);
+    if (!rc) rc = gtosi_attn_tile_set_seed_epoch(epoch);
     if (!rc) rc = gtosi_rowops_set_seed_epoch(epoch);
     if (!rc) rc = gtosi_gru_step_set_seed_epoch(epoch);
     if (!rc) rc = gtosi_tokenenc_set_seed_epoch(epoch);

@@ -865,6 +865,17 @@ class FactoredRelation:
         return y
 
 
+def _attn_tile_backward(mode, T_, d, H, lds, tensors):
+    """True when gtos_rel_attn_bwd will run this call on the MFMA tile kernels (attn_tile.hip), which keep P~ and dS on chip: the two
+    fp32 [T,S,B,H] hand-over buffers of the streaming passes are then not allocated.  Mirrors gtosi_attn_tile_covers; if the two ever
+    disagree the entry point returns -15 instead of reading a null buffer."""
+    if mode != 0 or os.environ.get("GTOS_ATTN_TILE", "1")[:1] == "0":
+        return False
+    if any(t.dtype != torch.bfloat16 or t.data_ptr() % 16 for t in tensors) or any(ld % 8 for ld in lds):
+        return False
+    return T_ >= 16 and d <= 512 and d & (d - 1) == 0 and d % H == 0 and d // H in (32, 64, 128)
+
+
 class RelAttnFn(torch.autograd.Function):
     """Fused (relation-aware) attention core.  qsrc [T,B,Cq] holds q at channel offset q_off; kvsrc [S,B,Ckv]
     (or qsrc itself when None) holds k, v at k_off, v_off.  rel: None | rarb [S,T,B,2d] | bank-projection [R,2d].
@@ -926,9 +937,12 @@ class RelAttnFn(torch.autograd.Function):
         else:
             d_rel = None
         ldr = d_rel.stride(0) if mode == 2 else 0
-        pd = torch.empty((T_, S, B, H), dtype=torch.float32, device=qsrc.device)
-        gs = torch.empty_like(pd)
         es = qsrc.element_size()
+        if _attn_tile_backward(mode, T_, d, H, (Cq, Ckv, d, q_off, k_off, v_off), (qsrc, kv, o, d_o, dqsrc, dkv)):
+            pd = gs = None
+        else:
+            pd = torch.empty((T_, S, B, H), dtype=torch.float32, device=qsrc.device)
+            gs = torch.empty_like(pd)
         with _Timed("rel_attn_bwd_q+kv_mode%d" % mode, detail=True):
             call("gtos_rel_attn_bwd", dt(qsrc), mode, T_, S, B, H, d,
                  qsrc.data_ptr() + q_off * es, Cq, kv.data_ptr() + k_off * es, Ckv, kv.data_ptr() + v_off * es, Ckv,

@@ -62,7 +62,9 @@ int gtos_gemm(int in_dtype, int out_dtype, int transA, int transB, int M, int N,
  * wave, per-head reductions as DPP butterflies.  Any other shape runs on the generic map: a head takes pow2ceil(d/H/8) lanes
  * (the surplus lanes idle), a key row as many heads as fit 64 lanes, the remaining heads further slices on blockIdx.y.  The
  * host modules refuse shapes outside at construction (gtos_amd.ops.check_attention_shape).
- * Modes 1,2 need T == S (-12). */
+ * Modes 1,2 need T == S (-12).
+ * Mode 0 in bf16 on the fast lane map with T >= 16 and a head of 32, 64 or 128 channels runs on MFMA tiles instead (attn_tile.hip: one
+ * workgroup per graph, head and 64 queries; same arguments, same dropout counters); GTOS_ATTN_TILE=0 keeps it on the streaming kernels. */
 int gtos_rel_attn_fwd(int dtype, int mode, int T, int S, int B, int H, int d,
                       const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                       const void* rel, const int* idx_q, const uint8_t* key_pad, const uint8_t* attn_mask,
@@ -75,7 +77,9 @@ int gtos_rel_attn_fwd(int dtype, int mode, int T, int S, int B, int H, int d,
  * mode 2 leaves the bank gradient to gtos_rel_attn_bwd_bank -- except for types whose id carries bit 31 in idx_q / idx_k
  * (set by the host index for types that occur exactly once in the batch): their single pair's term IS their bank gradient
  * row and is written straight into d_rel[type] (row stride ld_drel; d_rel may be NULL when no id is flagged).
- * pd/gs are caller-provided fp32 scratch [T,S,B,H] (post-dropout probabilities, scale*dS). */
+ * pd/gs are caller-provided fp32 scratch [T,S,B,H] (post-dropout probabilities, scale*dS).  The MFMA tile path of mode 0 (see
+ * gtos_rel_attn_fwd; one launch) keeps both on chip: pd and gs may be NULL for a call it covers, and -15 is returned when a call
+ * that needs them comes without. */
 int gtos_rel_attn_bwd(int dtype, int mode, int T, int S, int B, int H, int d,
                       const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                       const void* rel, const int* idx_q, const int* idx_k,
