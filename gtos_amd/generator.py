@@ -41,6 +41,17 @@ def check_sampling(samples, temperature, top_k, top_p, seed):
         raise ValueError("seed must be an integer or None, got %r" % (seed,))
 
 
+def check_no_repeat_ngram(n, search, max_time_step):
+    """The argument check of Generator.work(no_repeat_ngram=): ValueError unless n is an integer >= 0 and, for the device searches,
+    n and the step count fit the history row gtos_ngram_block stages (ops.NGRAM_MAX_T)."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+        raise ValueError("no_repeat_ngram must be an integer >= 0 (0 = off), got %r" % (n,))
+    if n and search != "host" and max(n, max_time_step) > ops.NGRAM_MAX_T:
+        raise ValueError("no_repeat_ngram with search=%r takes n and max_time_step up to %d, got n = %d, max_time_step = %d"
+                         % (search, ops.NGRAM_MAX_T, n, max_time_step))
+    return int(n)
+
+
 class Scores(collections.namedtuple("Scores", "sentence_ll tokens correct token_ll pred graph_of")):
     """What Generator.score returns, all DEVICE tensors over N scored sequences of at most T target positions (tokens + <END>):
     sentence_ll [N] fp64 = log p(sequence | graph), tokens [N] int32 (target positions), correct [N] int32 (positions whose argmax
@@ -174,14 +185,17 @@ class Generator(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ inference
     def work(self, data, beam_size, max_time_step, min_time_step=1, search="host", *, temperature=1.0, top_k=0, top_p=1.0,
-             seed=None):
+             seed=None, no_repeat_ngram=0):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
         step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
         "sample": gtos_amd.search.sample_device, ``beam_size`` independent samples per graph drawn with ``temperature``, ``top_k``
-        (0 = off, at most 32) and ``top_p`` from ``seed`` (None: ops.next_seed()); these four keywords belong to "sample" only."""
+        (0 = off, at most 32) and ``top_p`` from ``seed`` (None: ops.next_seed()); these four keywords belong to "sample" only.
+        ``no_repeat_ngram`` = n > 0 (any search): no hypothesis or sample repeats an n-gram of tokens -- the continuations that would
+        are scored -inf before the selection (the rule of csrc/ngram_kernels.h; on the device by gtos_ngram_block)."""
         if search not in ("host", "device", "sample"):
             raise ValueError("search must be 'host', 'device' or 'sample', got %r" % (search,))
+        no_repeat_ngram = check_no_repeat_ngram(no_repeat_ngram, search, max_time_step)
         if search == "sample":
             check_sampling(beam_size, temperature, top_k, top_p, seed)
             if seed is None:
@@ -204,12 +218,13 @@ class Generator(nn.Module):
                 'align_kv': dec.token_generator.alignment_layer.project_kv(concept_repr),
             }
             beams = [Beam(beam_size, min_time_step, max_time_step) for _ in range(concept_repr.size(1))]
+            block = dict(no_repeat_ngram=no_repeat_ngram) if no_repeat_ngram else {}       # n = 0: the calls as they always were
             if search == "device":
-                beam_search_device(self, memory, beams)
+                beam_search_device(self, memory, beams, **block)
             elif search == "sample":
-                sample_device(self, memory, beams, temperature, top_k, top_p, seed)
+                sample_device(self, memory, beams, temperature, top_k, top_p, seed, **block)
             else:
-                beam_search(self, beams, memory)
+                beam_search(self, beams, memory, **block)
         return beams
 
     # ------------------------------------------------------------------------------------------------ teacher-forced scoring
@@ -397,11 +412,12 @@ class Generator(nn.Module):
         token_char = torch.tensor([rows], dtype=torch.int64)
         return token.to(self.device), token_char.to(self.device)
 
-    def decode_step_batched(self, tokens, state, memory, beam_of_hyp, offset, topk):
+    def decode_step_batched(self, tokens, state, memory, beam_of_hyp, offset, topk, banned=None):
         """One step for N live hypotheses of ALL beams (what gtos_amd.search.beam_search drives).  tokens: their last token
         strings; state: None or {'snt': [cache per sentence-encoder layer], 'inf': [cache per inference layer]}, every cache
-        [t,N,2d]; memory: per GRAPH (``work``); beam_of_hyp [N]: graph index of each hypothesis.  Returns (state grown by one
-        row, per hypothesis the top-k [(token string, log-likelihood)])."""
+        [t,N,2d]; memory: per GRAPH (``work``); beam_of_hyp [N]: graph index of each hypothesis; banned: None or per hypothesis the output
+        ids whose ll is -inf before the top-k (search.banned_tokens).  Returns (state grown by one row, per hypothesis the top-k
+        [(token string, log-likelihood)])."""
         inp = self.prepare_incremental_input([[t] for t in tokens])
         sel = lambda v: v.index_select(1, beam_of_hyp)
         owners = beam_of_hyp.tolist()
@@ -410,7 +426,7 @@ class Generator(nn.Module):
                'snt_ext_kv': [sel(v) for v in memory['snt_ext_kv']], 'align_kv': sel(memory['align_kv']),
                'local_idx2token': [memory['local_idx2token'][bi] for bi in owners]}
         snt, inf, results = self._decode_core(inp, None if state is None else state['snt'], None if state is None else state['inf'],
-                                              mem, offset, topk)
+                                              mem, offset, topk, banned)
         return {'snt': snt, 'inf': inf}, results
 
     def _step_embed(self, inp, offset):
@@ -420,16 +436,23 @@ class Generator(nn.Module):
         ln = self.token_embed_layer_norm
         return ops.layer_norm_residual(x, None, ln.weight, ln.bias, 0.0, ln.eps)
 
-    def _decode_core(self, inp, snt_state, inf_state, mem, offset, topk):
+    def _decode_core(self, inp, snt_state, inf_state, mem, offset, topk, banned=None):
         """inp = (step_token [1,N], step_token_char [1,N,C]); snt_state / inf_state: per layer [t,N,2d] or None; mem: everything
-        already per hypothesis.  -> (new sentence-encoder caches, new inference caches, top-k results)."""
+        already per hypothesis; banned: None or per hypothesis the output ids that score -inf.  -> (new sentence-encoder caches, new
+        inference caches, top-k results)."""
         x = self._step_embed(inp, offset)
         snt_caches = []
         for li, layer in enumerate(self.snt_encoder.layers):
             x, c = layer.step(x, x, None if snt_state is None else snt_state[li], mem['snt_ext_kv'][li], mem['graph_padding_mask'])
             snt_caches.append(c)
         ll, inf_caches = self.decoder.step(mem['probe'], x, inf_state, mem)
-        topk_scores, topk_token = torch.topk(ll.squeeze(0).float(), topk, 1)
+        ll = ll.squeeze(0).float()
+        if banned is not None and any(banned):
+            rows = [h for h, ids in enumerate(banned) for _ in ids]
+            cols = [i for ids in banned for i in ids]
+            ll = ll.index_put((torch.tensor(rows, device=ll.device), torch.tensor(cols, device=ll.device)),
+                              torch.tensor(float('-inf'), device=ll.device))
+        topk_scores, topk_token = torch.topk(ll, topk, 1)
         vocab = self.vocabs['predictable_token']
         results = []
         for s, t, local in zip(topk_scores.tolist(), topk_token.tolist(), mem['local_idx2token']):

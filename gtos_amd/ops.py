@@ -1415,3 +1415,28 @@ def sample_step(t, k, V, tot, min_time_step, max_time_step, temperature, top_k, 
          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ll), max(ll.stride(0), tot), ptr(flag_shared), ptr(flag_local), ptr(owned_local),
          ptr(score), ptr(slot_state), ptr(tokens), ptr(active), ptr(tok_shared), ptr(tok_local), ptr(char_shared), ptr(char_local), C,
          int(dead_tok), ptr(dead_char), ptr(tok_out), ptr(char_out), stream())
+
+
+# ---------------------------------------------------------------------------------------------- repeat-n-gram blocking
+# (csrc/ngram.hip; gtos_amd.search._slot_decode launches it for both device decoders)
+NGRAM_MAX_T = 4096       # MAX_T of csrc/ngram_kernels.h: the longest history row the kernel stages
+
+
+def ngram_block(t, k, n, ll, parent, token, hist_prev, hist_cur, active):
+    """Before the selection of step t >= 1 (gtos_ngram_block): slot s's history hist_cur[s, :t] = hist_prev[parent[s], :t-1] + [token[s]]
+    (int32 [N, max_time_step]; parent / token int32 [N], what every slot took at step t - 1; parent None: a slot is its own parent)
+    and the columns of ll [N, tot] fp32 that would complete a repeated n-gram of it set to -inf, in place.  Slots with a negative
+    parent or token are left alone."""
+    require_cuda(ll, parent, token, hist_prev, hist_cur, active)
+    if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1:
+        raise _lib.GtosHipError("ngram_block: ll must be a 2-D fp32 tensor with unit column stride")
+    N, tot = ll.shape
+    max_t = hist_cur.shape[1]
+    assert hist_prev.shape == (N, max_t) and hist_cur.shape == (N, max_t) and hist_prev.dtype == torch.int32 and hist_cur.dtype == torch.int32
+    assert hist_prev.data_ptr() != hist_cur.data_ptr(), "ngram_block: the two history buffers alternate"
+    assert token.dtype == torch.int32 and token.numel() == N and (parent is None or (parent.dtype == torch.int32 and parent.numel() == N))
+    assert active.numel() == 3 and active.dtype == torch.int32
+    for x in (parent, token, hist_prev, hist_cur, active):
+        assert x is None or x.is_contiguous()
+    call("gtos_ngram_block", N, k, t, max_t, n, tot, ptr(ll), max(ll.stride(0), tot), ptr(parent), ptr(token), ptr(hist_prev),
+         ptr(hist_cur), ptr(active), stream())

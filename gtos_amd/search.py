@@ -84,23 +84,42 @@ class Beam(object):
         return self.completed_hypotheses[:k]
 
 
-def beam_search(model, beams, memory):
+def banned_tokens(y, n):
+    """The rule of csrc/ngram_kernels.h on a Python list: the tokens that would complete a repeated n-gram of y (n >= 1; n = 1: all of
+    y), in position order, repeats included."""
+    t = len(y)
+    suffix = y[t - n + 1:] if n > 1 else []
+    return [y[i + n - 1] for i in range(t - n + 1) if y[i:i + n - 1] == suffix]
+
+
+def beam_search(model, beams, memory, no_repeat_ngram=0):
     """Runs all beams to completion.  ``model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, topk)`` ->
-    (state, results); ``state`` is opaque here except that every tensor in it has the hypothesis axis at dim 1."""
+    (state, results); ``state`` is opaque here except that every tensor in it has the hypothesis axis at dim 1.  With
+    ``no_repeat_ngram`` = n > 0 the call also gets, per hypothesis, the output ids that would repeat an n-gram of its tokens
+    (banned_tokens on the strings after <STR>; string and id map one to one within a graph), which then score -inf."""
     device = memory['probe'].device
     state = None
+    if no_repeat_ngram:
+        pv = model.vocabs['predictable_token']
+        copy_id = [{w: i for i, w in local.items()} for local in memory['local_idx2token']]
     while True:
-        owners, tokens = [], []
+        owners, tokens, banned = [], [], []
         for bi, beam in enumerate(beams):
             if not beam.completed():
                 for hyp in beam.hypotheses:
                     owners.append(bi)
                     tokens.append(hyp.seq[-1])
                     offset = len(hyp.seq) - 1
+                    if no_repeat_ngram:
+                        banned.append([copy_id[bi][w] if w in copy_id[bi] else pv.token2idx(w)
+                                       for w in banned_tokens(hyp.seq[1:], no_repeat_ngram)])
         if not owners:
             break
         beam_of_hyp = torch.tensor(owners, dtype=torch.int64, device=device)
-        state, results = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size)
+        if no_repeat_ngram:
+            state, results = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size, banned)
+        else:
+            state, results = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size)
         # hand every beam its slice of the results; collect the flat parent index of each survivor
         keep, pos = [], 0
         for bi, beam in enumerate(beams):
@@ -135,7 +154,7 @@ def _arena(dtype, cuts, dev):
     return views, lambda: {cut[0]: part.tolist() for cut, part in zip(cuts, torch.split(flat.cpu(), sizes))}
 
 
-def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, layout, step, fill):
+def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, layout, step, fill, no_repeat_ngram=0, taken=None):
     """The fixed-slot decode loop (the contract of csrc/slot_kernels.h) behind ``who``, a public function: B graphs x k slots, N = B*k,
     slot s belongs to graph s // k, the graph memory gathered per slot once, every slot decoded every step (a dead slot on the
     padding input), the input of step t + 1 written by step t's kernels into the other of two buffers.  The loop reads the device's
@@ -147,7 +166,10 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
         d holds B, k, N, min_t, max_t, V, tot, local, tab (Generator.search_tables) and then arr, the views by name with ``active``;
       step(d, t, ll, cur, nxt, tok_out, char_out): step t's launches after the decoder's, ll [N, tot] fp32; cur / nxt: the caches
         read and those step t + 1 reads (the same with one copy); tok_out [N] / char_out [N,C]: step t + 1's input, for EVERY slot;
-      fill(beams, k, token_string=, **tables) -> the Beam objects from its tables as flat lists; token_string(b, id) -> the string."""
+      fill(beams, k, token_string=, **tables) -> the Beam objects from its tables as flat lists; token_string(b, id) -> the string;
+      taken(d, t) -> (parent [N] int32 or None, token [N] int32): what every slot took at step t (a negative entry: a dead slot), for
+        ``no_repeat_ngram`` = n > 0, the rule of csrc/ngram_kernels.h: two int32 [N, max_t] history buffers alternate by step parity and
+        ops.ngram_block bans, in ll, the columns that would repeat an n-gram, at every step t >= 1 before step().  n = 0: nothing of it."""
     B = len(beams)
     if not B:
         return beams
@@ -179,9 +201,13 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     chars = [tab['dead_char'].expand(1, N, C).contiguous() for _ in range(2)]
     tok[0].view(B, k)[:, :live0] = tab['start_tok']
     chars[0].view(B, k, C)[:, :live0] = tab['start_char']
+    hist = [torch.zeros((N, max_t), dtype=torch.int32, device=dev) for _ in range(2)] if no_repeat_ngram else None
     for t in range(max_t):
         cur, nxt = t % 2, (t + 1) % 2
         ll = model.decode_slots((tok[cur], chars[cur]), caches[cur % copies], mem, t)
+        if no_repeat_ngram and t:
+            parent, token = taken(d, t - 1)
+            ops.ngram_block(t, k, no_repeat_ngram, ll, parent, token, hist[nxt], hist[cur], ints['active'])
         step(d, t, ll, caches[cur % copies], caches[nxt % copies], tok[nxt][0], chars[nxt][0])
         n_steps += 1
         if (t + 1) % sync_every == 0 and t + 1 < max_t:
@@ -197,12 +223,12 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     return fill(beams, k, token_string=lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i), **host)
 
 
-def beam_search_device(model, memory, beams, sync_every=8, stats=None):
+def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0):
     """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
     decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
     steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
     keep computing on the padding input and zero cache rows, their candidates are ignored.  The continue flag is "some not-done
-    beam has a live slot"; ``sync_every`` and ``stats`` as in _slot_decode.  The Beam objects are filled as beam_search leaves them
+    beam has a live slot"; ``sync_every``, ``stats`` and ``no_repeat_ngram`` as in _slot_decode.  The Beam objects are filled as beam_search leaves them
     (hypotheses, completed_hypotheses in append order, steps)."""
     def layout(d):
         return ([('state', (d.B, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
@@ -215,7 +241,8 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None):
                          a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'], a['active'])
         ops.beam_reorder(cur, nxt, t, d.k, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
                          tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
-    return _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill_beams)
+    return _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill_beams, no_repeat_ngram,
+                        lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]))
 
 
 def slot_memory(memory, B, k):
@@ -264,12 +291,12 @@ def sample_bits(seed, graph, sample, t, cols):
     return SplitMix64(key).u64(int(cols.max()) + 1 if cols.size else 0)[cols]
 
 
-def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_every=8, stats=None):
+def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_every=8, stats=None, no_repeat_ngram=0):
     """Sampling decode on the device (csrc/sample.hip), the counterpart of beam_search_device with the same ``memory``: every graph
     gets ``beam_size`` independent samples in fixed slots (slot s is sample s % k of graph s // k), each drawing its next token by the
     rule of csrc/sample_kernels.h (temperature, top_k, top_p; <UNK>, other graphs' copy ids and <END> before min_time_step are never
     drawn) from a counter hash of (seed, graph, sample, step, column).  A sample never changes parent, so each layer keeps ONE
-    [max_time_step, N, 2d] cache and nothing is reordered; ``sync_every`` and ``stats`` as in _slot_decode.  Returns the beams filled
+    [max_time_step, N, 2d] cache and nothing is reordered; ``sync_every``, ``stats`` and ``no_repeat_ngram`` as in _slot_decode.  Returns the beams filled
     like a beam search's: completed_hypotheses (ended by <END>) by completion step, then sample index; hypotheses (unfinished) in
     sample order; score = the fp64 sum of the model's ll of the drawn tokens."""
     def layout(d):
@@ -281,7 +308,8 @@ def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_ev
         ops.sample_step(t, d.k, d.V, d.tot, d.min_t, d.max_t, temperature, top_k, top_p, seed, ll, tab['flag_shared'], tab['flag_local'],
                         d.owned, a['score'], a['state'], a['tokens'], a['active'], tab['tok_shared'], tab['tok_local'],
                         tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
-    return _slot_decode("sample_device", model, memory, beams, sync_every, stats, 1, None, layout, step, fill_samples)
+    return _slot_decode("sample_device", model, memory, beams, sync_every, stats, 1, None, layout, step, fill_samples, no_repeat_ngram,
+                        lambda d, t: (None, d.arr['tokens'][t]))
 
 
 def fill_samples(beams, k, state, tokens, score, token_string):

@@ -480,6 +480,24 @@ int gtos_sample_step(int N, int k, int t, int V, int tot, int min_time_step, int
                      const int64_t* char_local, int C, int64_t dead_tok, const int64_t* dead_char, int64_t* tok_out,
                      int64_t* char_out, void* stream);
 
+/* ---- Repeat-n-gram blocking of the device-resident decoders (ABI 26; csrc/ngram.hip, the rule in csrc/ngram_kernels.h), driven by
+ * gtos_amd.search._slot_decode for both of them: the constraint generation toolkits call no_repeat_ngram_size.  A slot that has
+ * generated y[0, t) (output ids) may not complete an n-gram it already holds: for every i in [0, t - n] with
+ * y[i .. i+n-2] == y[t-n+1 .. t-1], column y[i+n-1] of its ll row becomes -inf (n = 1: every token generated so far).  The rule has
+ * no counterpart in generator/search.py; it is stated in full in csrc/ngram_kernels.h.
+ * _block is launched once per step t >= 1, after the decoder's ll [N, tot] fp32 (row stride ld >= tot) and before the step's
+ *   selection.  parent / token int32 [N]: the parent slot and the token id every slot took at step t - 1 (row t - 1 of bp_parent /
+ *   bp_token; for the sampler parent = NULL, a slot is its own parent, and row t - 1 of tokens).  A slot with parent < 0 or
+ *   token < 0 is dead: its ll row and its hist_cur row are left as they are.  A live slot s gets hist_cur[s, 0 .. t-2] =
+ *   hist_prev[parent, 0 .. t-2] and hist_cur[s, t-1] = token[s] (int32 [N, max_time_step] each; the caller alternates the two buffers
+ *   by step parity, a slot reads its parent's row while the parent's owner rewrites its own), then the bans of that t-token history
+ *   in ll[s, :], written in place; every other element of ll and hist_cur[s, t:] stay as they are.  active int32 [3] as in
+ *   csrc/slot_kernels.h, read only: a step that does not run writes nothing.
+ *   SHAPES (-10 outside): n >= 1, 1 <= t < max_time_step <= 4096 (one history row in LDS), tot >= 1, ld >= tot, N % k == 0;
+ *   -23 for a null pointer other than parent. */
+int gtos_ngram_block(int N, int k, int t, int max_time_step, int n, int tot, float* ll, int64_t ld, const int* parent,
+                     const int* token, const int* hist_prev, int* hist_cur, const int* active, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
