@@ -3,6 +3,7 @@
 // the next step's input token ids and character rows.  Nothing here synchronises with the host; the per-beam state, back-pointers and
 // completions stay on the device until the search ends.
 #include "beam_kernels.h"
+#include "reorder_device.h"
 #include "slot_device.h"
 
 using namespace gtos_beam;
@@ -70,52 +71,6 @@ __global__ __launch_bounds__(NT) void beam_advance_kernel(AdvanceArgs a) {
     }
 }
 
-constexpr int MAX_CACHES = 32;
-
-struct ReorderArgs {
-    int n, N, k, t, V, tot;
-    int64_t q;                          // 16-byte pieces per cache row
-    const uint4* src[MAX_CACHES];
-    uint4* dst[MAX_CACHES];
-    const int* bp_parent_t;             // row t of the back-pointer tables
-    const int* bp_token_t;
-    const int* state;
-    const int* active_t;                // the flag step t's advance read
-    NextInput next;
-};
-
-__device__ __forceinline__ bool slot_live(const ReorderArgs& a, int s) {
-    return a.bp_parent_t[s] >= 0 && !a.state[(int64_t)(s / a.k) * BS_WORDS + BS_DONE];
-}
-
-// blockIdx.y < n: cache y, rows [0, t] gathered by parent slot into the other buffer of its pair (dead slots: zero rows);
-// blockIdx.y == n: the next step's input token id and character row of every slot (dead slots: the padding input).
-// After an iteration that did not run, the caches are left as they are and every slot gets the padding input.
-__global__ __launch_bounds__(NT) void beam_reorder_kernel(ReorderArgs a) {
-    const bool act = *a.active_t != 0;
-    const int64_t stride = (int64_t)gridDim.x * NT;
-    if ((int)blockIdx.y == a.n) {
-        const int C1 = a.next.C + 1;
-        for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < (int64_t)a.N * C1; e += stride) {
-            const int s = (int)(e / C1);
-            write_next_input(a.next, a.V, a.tot, s / a.k, s, (int)(e % C1) - 1, act && slot_live(a, s) ? a.bp_token_t[s] : -1);
-        }
-        return;
-    }
-    if (!act) return;
-    const uint4* src = a.src[blockIdx.y];
-    uint4* dst = a.dst[blockIdx.y];
-    const int64_t total = (int64_t)(a.t + 1) * a.N * a.q;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < total; e += stride) {
-        const int64_t rowi = e / a.q, c = e % a.q;
-        const int s = (int)(rowi % a.N);
-        const int64_t r = rowi / a.N;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (slot_live(a, s)) v = src[(r * a.N + a.bp_parent_t[s]) * a.q + c];
-        dst[e] = v;
-    }
-}
-
 }  // namespace
 
 extern "C" int gtos_beam_topk(int rows, int tot, int k, const float* ll, int64_t ld, float* val, int* idx, void* stream) {
@@ -154,25 +109,6 @@ extern "C" int gtos_beam_reorder(int n_caches, void* const* src, void* const* ds
                                  const int* active, int V, int tot, const int64_t* tok_shared, const int64_t* tok_local,
                                  const int64_t* char_shared, const int64_t* char_local, int C, int64_t dead_tok,
                                  const int64_t* dead_char, int64_t* tok_out, int64_t* char_out, void* stream) {
-    if (N <= 0) return 0;
-    if (n_caches < 0 || n_caches > MAX_CACHES || row_bytes <= 0 || row_bytes % 16 || k < 1 || k > MAX_K || N % k || t < 0 ||
-        t >= max_time_step || V < 1 || tot < V || C < 1)
-        return -10;
-    ReorderArgs a{};
-    a.next = NextInput{tok_shared, tok_local, char_shared, char_local, dead_tok, dead_char, C, tok_out, char_out};
-    if ((n_caches && (!src || !dst)) || !bp_parent || !bp_token || !beam_state || !active || !next_input_ok(a.next, V, tot)) return -23;
-    a.n = n_caches; a.N = N; a.k = k; a.t = t; a.V = V; a.tot = tot; a.q = row_bytes / 16;
-    for (int i = 0; i < n_caches; ++i) {
-        if (!src[i] || !dst[i] || (uintptr_t)src[i] % 16 || (uintptr_t)dst[i] % 16 || src[i] == dst[i]) return -25;
-        a.src[i] = static_cast<const uint4*>(src[i]);
-        a.dst[i] = static_cast<uint4*>(dst[i]);
-    }
-    a.bp_parent_t = bp_parent + (int64_t)t * N; a.bp_token_t = bp_token + (int64_t)t * N; a.state = beam_state;
-    a.active_t = active + active_read(t);
-    const int64_t work = (int64_t)(t + 1) * N * a.q;
-    const int64_t blocks = (work + NT - 1) / NT;
-    const unsigned gx = (unsigned)(blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks);
-    hipLaunchKernelGGL(beam_reorder_kernel, dim3(gx, (unsigned)n_caches + 1), dim3(NT), 0, static_cast<hipStream_t>(stream), a);
-    GTOS_CHECK_LAUNCH();
-    return 0;
+    return reorder_launch(n_caches, src, dst, row_bytes, N, k, k, t, max_time_step, bp_parent, bp_token, beam_state, active, V, tot,
+                          NextInput{tok_shared, tok_local, char_shared, char_local, dead_tok, dead_char, C, tok_out, char_out}, stream);
 }

@@ -52,6 +52,24 @@ def check_no_repeat_ngram(n, search, max_time_step):
     return int(n)
 
 
+def check_groups(groups, diversity, beam_size, search):
+    """The argument checks of Generator.work(groups=, diversity=): ValueError unless groups is an integer >= 1 that divides beam_size
+    and diversity a finite real >= 0; both belong to the beam searches, and a penalty without groups would do nothing."""
+    if isinstance(groups, bool) or not isinstance(groups, numbers.Integral) or groups < 1:
+        raise ValueError("groups must be an integer >= 1, got %r" % (groups,))
+    if isinstance(diversity, bool) or not isinstance(diversity, numbers.Real) or not 0 <= diversity < math.inf:
+        raise ValueError("diversity must be a finite number >= 0, got %r" % (diversity,))
+    if search == "sample":
+        if groups != 1 or diversity != 0:
+            raise ValueError("groups and diversity apply to the beam searches, not to search='sample'")
+        return 1, 0.0
+    if isinstance(beam_size, bool) or not isinstance(beam_size, numbers.Integral) or beam_size < 1 or beam_size % groups:
+        raise ValueError("groups must divide beam_size, got groups = %r, beam_size = %r" % (groups, beam_size))
+    if diversity > 0 and groups == 1:
+        raise ValueError("diversity = %r with groups = 1 would do nothing: ask for groups > 1" % (diversity,))
+    return int(groups), float(diversity)
+
+
 class Scores(collections.namedtuple("Scores", "sentence_ll tokens correct token_ll pred graph_of")):
     """What Generator.score returns, all DEVICE tensors over N scored sequences of at most T target positions (tokens + <END>):
     sentence_ll [N] fp64 = log p(sequence | graph), tokens [N] int32 (target positions), correct [N] int32 (positions whose argmax
@@ -185,17 +203,23 @@ class Generator(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ inference
     def work(self, data, beam_size, max_time_step, min_time_step=1, search="host", *, temperature=1.0, top_k=0, top_p=1.0,
-             seed=None, no_repeat_ngram=0):
+             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
         step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
         "sample": gtos_amd.search.sample_device, ``beam_size`` independent samples per graph drawn with ``temperature``, ``top_k``
         (0 = off, at most 32) and ``top_p`` from ``seed`` (None: ops.next_seed()); these four keywords belong to "sample" only.
         ``no_repeat_ngram`` = n > 0 (any search): no hypothesis or sample repeats an n-gram of tokens -- the continuations that would
-        are scored -inf before the selection (the rule of csrc/ngram_kernels.h; on the device by gtos_ngram_block)."""
+        are scored -inf before the selection (the rule of csrc/ngram_kernels.h; on the device by gtos_ngram_block).
+        ``groups`` = G > 1 ("host" and "device"): diverse beam search -- the beam_size hypotheses of a graph are G groups of
+        beam_size / G that search one after the other, a group's selection lowering every candidate by ``diversity`` for each
+        hypothesis of the groups before it that took the same token at this step (gtos_amd.search.GroupBeam, the rule of
+        csrc/diverse_kernels.h; on the device by gtos_diverse_advance / gtos_diverse_reorder).  Scores stay log-likelihoods.  A
+        returned beam then carries ``groups``, G Beam objects of width beam_size / G, and its own lists are theirs in group order."""
         if search not in ("host", "device", "sample"):
             raise ValueError("search must be 'host', 'device' or 'sample', got %r" % (search,))
         no_repeat_ngram = check_no_repeat_ngram(no_repeat_ngram, search, max_time_step)
+        groups, diversity = check_groups(groups, diversity, beam_size, search)
         if search == "sample":
             check_sampling(beam_size, temperature, top_k, top_p, seed)
             if seed is None:
@@ -219,6 +243,8 @@ class Generator(nn.Module):
             }
             beams = [Beam(beam_size, min_time_step, max_time_step) for _ in range(concept_repr.size(1))]
             block = dict(no_repeat_ngram=no_repeat_ngram) if no_repeat_ngram else {}       # n = 0: the calls as they always were
+            if groups != 1:                                                                # groups = 1: likewise
+                block.update(groups=groups, diversity=diversity)
             if search == "device":
                 beam_search_device(self, memory, beams, **block)
             elif search == "sample":

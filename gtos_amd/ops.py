@@ -1321,7 +1321,7 @@ def eval_accumulate(nll, pred, target, pad_idx, totals):
 
 
 # ---------------------------------------------------------------------------------------------- device-resident beam search
-# (csrc/beam.hip; gtos_amd.search.beam_search_device drives them)
+# (csrc/beam.hip and, for the grouped search, csrc/diverse.hip; gtos_amd.search.beam_search_device drives them)
 def beam_topk(ll, k):
     """ll [rows, tot] fp32 (row stride >= tot, unit column stride) -> (values [rows,k] fp32, columns [rows,k] int32), descending,
     equal values lower column first."""
@@ -1354,6 +1354,29 @@ def beam_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, flag_sh
          ptr(active), stream())
 
 
+def diverse_advance(t, k, groups, diversity, V, tot, min_time_step, max_time_step, topv, topi, flag_shared, flag_local, slot_score,
+                    group_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
+    """One advance of every graph's ``groups`` groups at step t (gtos_diverse_advance, the rule of csrc/diverse_kernels.h): beam_advance
+    with group_state int32 [B*groups, 4] (or [B, groups, 4]) and the fp64 penalty weight ``diversity``; the other tables as there."""
+    import struct
+    assert groups >= 1 and k % groups == 0 and group_state.numel() % (4 * groups) == 0
+    B = group_state.numel() // (4 * groups)
+    N = B * k
+    require_cuda(topv, topi, flag_shared, slot_score, group_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active)
+    assert topv.shape == (N, k) and topi.shape == (N, k) and topv.dtype == torch.float32 and topi.dtype == torch.int32
+    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
+    assert flag_local is None or (flag_local.dtype == torch.uint8 and flag_local.numel() >= B * (tot - V))
+    assert slot_score.dtype == torch.float64 and slot_score.numel() == N and group_state.shape[-1] == 4 and group_state.dtype == torch.int32
+    assert bp_parent.shape == (max_time_step, N) and bp_token.shape == (max_time_step, N)
+    assert comp_step.shape == (B, k) and comp_parent.shape == (B, k) and comp_score.shape == (B, k) and active.numel() == 3
+    for x in (topv, topi, flag_shared, flag_local, slot_score, group_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
+        assert x is None or x.is_contiguous()
+    bits = struct.unpack("<Q", struct.pack("<d", float(diversity)))[0]
+    call("gtos_diverse_advance", B, k, groups, bits, t, V, tot, min_time_step, max_time_step, ptr(topv), ptr(topi), ptr(flag_shared),
+         ptr(flag_local), ptr(slot_score), ptr(group_state), ptr(bp_parent), ptr(bp_token), ptr(comp_step), ptr(comp_parent),
+         ptr(comp_score), ptr(active), stream())
+
+
 def _check_next_input(N, k, V, tot, tok_shared, tok_local, char_shared, char_local, dead_char, tok_out, char_out):
     """The next-input table group of beam_reorder / sample_step (NextInput in csrc/slot_device.h): int64, contiguous, sized for N
     slots of k per graph, ids [0, V) shared and [V, tot) per graph, C characters.  -> C"""
@@ -1368,14 +1391,13 @@ def _check_next_input(N, k, V, tot, tok_shared, tok_local, char_shared, char_loc
     return C
 
 
-def beam_reorder(src, dst, t, k, bp_parent, bp_token, beam_state, active, V, tot, tok_shared, tok_local, char_shared, char_local,
-                 dead_tok, dead_char, tok_out, char_out):
-    """After the advance of step t: rows [0,t] of every cache src[i] ([T_max, N, w], contiguous) gathered by parent slot into dst[i],
-    and the next input (tok_out [N] int64, char_out [N,C] int64) of every slot (gtos_beam_reorder)."""
+def _reorder_call(name, src, dst, t, k, width, bp_parent, bp_token, state, active, V, tot, tok_shared, tok_local, char_shared, char_local,
+                  dead_tok, dead_char, tok_out, char_out):
+    """The operand checks and the call of gtos_beam_reorder (width None) / gtos_diverse_reorder (width = the group width)."""
     import ctypes
     T_max, N = bp_parent.shape
     C = _check_next_input(N, k, V, tot, tok_shared, tok_local, char_shared, char_local, dead_char, tok_out, char_out)
-    require_cuda(bp_parent, bp_token, beam_state, active, *src, *dst)
+    require_cuda(bp_parent, bp_token, state, active, *src, *dst)
     row_bytes = 0
     for a, b in zip(src, dst):
         assert a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous()
@@ -1387,9 +1409,28 @@ def beam_reorder(src, dst, t, k, bp_parent, bp_token, beam_state, active, V, tot
     n = len(src)
     S = (ctypes.c_void_p * max(1, n))(*[x.data_ptr() for x in src])
     D = (ctypes.c_void_p * max(1, n))(*[x.data_ptr() for x in dst])
-    call("gtos_beam_reorder", n, ctypes.addressof(S), ctypes.addressof(D), row_bytes or 16, N, k, t, T_max, ptr(bp_parent), ptr(bp_token),
-         ptr(beam_state), ptr(active), V, tot, ptr(tok_shared), ptr(tok_local), ptr(char_shared), ptr(char_local), C, int(dead_tok),
-         ptr(dead_char), ptr(tok_out), ptr(char_out), stream())
+    call(name, n, ctypes.addressof(S), ctypes.addressof(D), row_bytes or 16, N, k, *(() if width is None else (width,)), t, T_max,
+         ptr(bp_parent), ptr(bp_token), ptr(state), ptr(active), V, tot, ptr(tok_shared), ptr(tok_local), ptr(char_shared),
+         ptr(char_local), C, int(dead_tok), ptr(dead_char), ptr(tok_out), ptr(char_out), stream())
+
+
+def beam_reorder(src, dst, t, k, bp_parent, bp_token, beam_state, active, V, tot, tok_shared, tok_local, char_shared, char_local,
+                 dead_tok, dead_char, tok_out, char_out):
+    """After the advance of step t: rows [0,t] of every cache src[i] ([T_max, N, w], contiguous) gathered by parent slot into dst[i],
+    and the next input (tok_out [N] int64, char_out [N,C] int64) of every slot (gtos_beam_reorder)."""
+    _reorder_call("gtos_beam_reorder", src, dst, t, k, None, bp_parent, bp_token, beam_state, active, V, tot, tok_shared, tok_local,
+                  char_shared, char_local, dead_tok, dead_char, tok_out, char_out)
+
+
+def diverse_reorder(src, dst, t, k, width, bp_parent, bp_token, group_state, active, V, tot, tok_shared, tok_local, char_shared,
+                    char_local, dead_tok, dead_char, tok_out, char_out):
+    """beam_reorder after a diverse_advance (gtos_diverse_reorder): slot s is live by the state words of its group s // width
+    (group_state int32 [N // width, 4], contiguous), its copy ids resolve through the tables of its graph s // k."""
+    N = bp_parent.shape[1]
+    assert width >= 1 and k % width == 0 and N % k == 0
+    assert group_state.dtype == torch.int32 and group_state.numel() == N // width * 4 and group_state.is_contiguous()
+    _reorder_call("gtos_diverse_reorder", src, dst, t, k, width, bp_parent, bp_token, group_state, active, V, tot, tok_shared, tok_local,
+                  char_shared, char_local, dead_tok, dead_char, tok_out, char_out)
 
 
 # ---------------------------------------------------------------------------------------------- device-resident sampling decode

@@ -16,6 +16,10 @@ instead of being split into per-hypothesis slices and concatenated again.
 hypothesis slots, the graph memory gathered per slot once, preallocated caches reordered by a kernel, and the host reading one
 flag every ``sync_every`` steps and the back-pointer / completion tables once at the end.
 
+``groups`` / ``diversity`` turn either beam search into diverse (group) beam search (GroupBeam; on the device csrc/diverse.hip, the
+rule in csrc/diverse_kernels.h): the k hypotheses of a sentence are cut into groups that search one after the other, each steered away
+from the tokens the groups before it took at the same step.
+
 ``sample_device`` decodes by sampling instead (csrc/sample.hip): the same fixed slots, one independent sample per slot with
 temperature / top-k / top-p, and Beam objects filled the same way.
 """
@@ -84,6 +88,78 @@ class Beam(object):
         return self.completed_hypotheses[:k]
 
 
+class GroupBeam(Beam):
+    """Diverse (group) beam search of one sentence (Vijayakumar et al., "Diverse Beam Search", Hamming penalty): the rule of
+    csrc/diverse_kernels.h in Python.  ``groups`` Beam objects of width g = beam_size / groups, each a search of its own (steps,
+    completions, done when it holds g completions or after max_time_step steps).  A step takes the groups in order with a list of the
+    tokens chosen so far in this step: a group sorts its pool by ``score - diversity * chosen.count(token)`` (stable, descending),
+    cuts and places it as Beam.advance does, and the tokens of its surviving hypotheses join the list.  A hypothesis's score stays
+    the model's log-likelihood; the penalty only steers the selection.  ``hypotheses`` / ``completed_hypotheses`` are the groups'
+    lists in group order, ``steps`` the most of any group."""
+
+    def __init__(self, beam_size, min_time_step, max_time_step, groups, diversity):
+        assert groups >= 1 and beam_size % groups == 0 and 0 <= diversity < float('inf')
+        super().__init__(beam_size, min_time_step, max_time_step)
+        self.diversity = float(diversity)
+        self.groups = [Beam(beam_size // groups, min_time_step, max_time_step) for _ in range(groups)]
+        self.last_parents = [None] * groups
+        gather_groups(self, self.groups)
+
+    def live_hypotheses(self):
+        """The hypotheses the next step decodes: those of the groups that are not completed, in group order."""
+        return [h for grp in self.groups if not grp.completed() for h in grp.hypotheses]
+
+    def completed(self):
+        return all(grp.completed() for grp in self.groups)
+
+    def advance(self, last_steps):
+        """last_steps[h] = [(token, log-likelihood), ...] (the top beam_size, in rank order) for h in live_hypotheses().  Returns the
+        index into that list of the parent of every hypothesis of the next live_hypotheses(), in its order; ``last_parents[j]``
+        keeps group j's parents as indices into its own old hypotheses (None for a group that was completed before the step)."""
+        chosen, keep, pos = [], [], 0
+        self.last_parents = [None] * len(self.groups)
+        for j, grp in enumerate(self.groups):
+            if grp.completed():
+                continue
+            n = len(grp.hypotheses)
+            pool = []
+            for parent, steps in enumerate(last_steps[pos:pos + n]):
+                base = grp.hypotheses[parent].score
+                for token, ll in steps:
+                    score = float('-inf') if token == UNK else base + ll
+                    pool.append((parent, token, score, score - self.diversity * chosen.count(token)))
+            pool.sort(key=lambda c: c[3], reverse=True)                 # stable: ties keep (parent, rank) order
+            pool = pool[:grp.beam_size - len(grp.completed_hypotheses)]
+            alive, parents = [], []
+            for parent, token, score, _ in pool:
+                hyp = Hypothesis(grp.hypotheses[parent].seq + [token], score)
+                if hyp.is_completed():
+                    if len(hyp) - 2 >= grp.min_time_step:
+                        grp.completed_hypotheses.append(hyp)
+                else:
+                    alive.append(hyp)
+                    parents.append(parent)
+                    chosen.append(token)
+            grp.hypotheses = alive
+            grp.steps += 1
+            self.last_parents[j] = parents
+            if not grp.completed():
+                keep.extend(pos + p for p in parents)
+            pos += n
+        gather_groups(self, self.groups)
+        return keep
+
+
+def gather_groups(beam, groups):
+    """``beam`` (width k) as the result of a grouped search over ``groups`` (Beam objects of width k / G): the attribute ``groups``,
+    the groups' hypothesis lists concatenated in group order, the most steps of any group."""
+    beam.groups = groups
+    beam.hypotheses = [h for grp in groups for h in grp.hypotheses]
+    beam.completed_hypotheses = [h for grp in groups for h in grp.completed_hypotheses]
+    beam.steps = max(grp.steps for grp in groups)
+    return beam
+
+
 def banned_tokens(y, n):
     """The rule of csrc/ngram_kernels.h on a Python list: the tokens that would complete a repeated n-gram of y (n >= 1; n = 1: all of
     y), in position order, repeats included."""
@@ -92,13 +168,21 @@ def banned_tokens(y, n):
     return [y[i + n - 1] for i in range(t - n + 1) if y[i:i + n - 1] == suffix]
 
 
-def beam_search(model, beams, memory, no_repeat_ngram=0):
+def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0):
     """Runs all beams to completion.  ``model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, topk)`` ->
     (state, results); ``state`` is opaque here except that every tensor in it has the hypothesis axis at dim 1.  With
     ``no_repeat_ngram`` = n > 0 the call also gets, per hypothesis, the output ids that would repeat an n-gram of its tokens
-    (banned_tokens on the strings after <STR>; string and id map one to one within a graph), which then score -inf."""
+    (banned_tokens on the strings after <STR>; string and id map one to one within a graph), which then score -inf.
+    ``groups`` / ``diversity`` other than (1, 0.0): diverse beam search -- every (fresh) beam is searched as a GroupBeam of its
+    settings and then holds that search's result (gather_groups)."""
     device = memory['probe'].device
     state = None
+    result = beams
+    if groups != 1 or diversity != 0.0:
+        beams = [GroupBeam(b.beam_size, b.min_time_step, b.max_time_step, groups, diversity) for b in beams]
+        live = GroupBeam.live_hypotheses
+    else:
+        live = lambda beam: beam.hypotheses
     if no_repeat_ngram:
         pv = model.vocabs['predictable_token']
         copy_id = [{w: i for i, w in local.items()} for local in memory['local_idx2token']]
@@ -106,7 +190,7 @@ def beam_search(model, beams, memory, no_repeat_ngram=0):
         owners, tokens, banned = [], [], []
         for bi, beam in enumerate(beams):
             if not beam.completed():
-                for hyp in beam.hypotheses:
+                for hyp in live(beam):
                     owners.append(bi)
                     tokens.append(hyp.seq[-1])
                     offset = len(hyp.seq) - 1
@@ -125,7 +209,7 @@ def beam_search(model, beams, memory, no_repeat_ngram=0):
         for bi, beam in enumerate(beams):
             if beam.completed():
                 continue
-            n = len(beam.hypotheses)
+            n = len(live(beam))
             parents = beam.advance(results[pos:pos + n])
             if not beam.completed():
                 keep.extend(pos + p for p in parents)
@@ -134,7 +218,10 @@ def beam_search(model, beams, memory, no_repeat_ngram=0):
             break
         idx = torch.tensor(keep, dtype=torch.int64, device=device)
         state = {k: [c.index_select(1, idx) for c in v] for k, v in state.items()}
-    return beams
+    if result is not beams:
+        for beam, run in zip(result, beams):
+            gather_groups(beam, run.groups)
+    return result
 
 
 def _arena(dtype, cuts, dev):
@@ -161,7 +248,8 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     continue flag ``active`` every ``sync_every`` steps (steps past the end are no-ops) and the tables once at the end, one copy per
     arena; ``stats`` (a dict, optional) receives the decoder steps launched and the host reads made.  A decoder supplies
       copies: buffers per self-attention cache (Generator.slot_caches), 2 when step() reorders one into the other;
-      live0: slots per graph that start on <STR>, the rest on the padding input (None: all k);
+      live0: slots per graph that start on <STR>, the rest on the padding input (None: all k); a pair (g, n): the first n slots of
+        every g consecutive ones;
       layout(d) -> (int32 cuts, fp64 cuts) of its tables, as _arena takes them (also the place to hang tables of its own on d);
         d holds B, k, N, min_t, max_t, V, tot, local, tab (Generator.search_tables) and then arr, the views by name with ``active``;
       step(d, t, ll, cur, nxt, tok_out, char_out): step t's launches after the decoder's, ll [N, tot] fp32; cur / nxt: the caches
@@ -199,8 +287,9 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     caches = [[c[i] for c in caches] for i in range(copies)]
     tok = [torch.full((1, N), tab['dead_tok'], dtype=torch.int64, device=dev) for _ in range(2)]
     chars = [tab['dead_char'].expand(1, N, C).contiguous() for _ in range(2)]
-    tok[0].view(B, k)[:, :live0] = tab['start_tok']
-    chars[0].view(B, k, C)[:, :live0] = tab['start_char']
+    width, live0 = live0 if isinstance(live0, tuple) else (k, live0)
+    tok[0].view(B, k // width, width)[:, :, :live0] = tab['start_tok']
+    chars[0].view(B, k // width, width, C)[:, :, :live0] = tab['start_char']
     hist = [torch.zeros((N, max_t), dtype=torch.int32, device=dev) for _ in range(2)] if no_repeat_ngram else None
     for t in range(max_t):
         cur, nxt = t % 2, (t + 1) % 2
@@ -223,13 +312,22 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     return fill(beams, k, token_string=lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i), **host)
 
 
-def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0):
+def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0, groups=1, diversity=0.0, grouped=None):
     """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
     decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
     steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
     keep computing on the padding input and zero cache rows, their candidates are ignored.  The continue flag is "some not-done
     beam has a live slot"; ``sync_every``, ``stats`` and ``no_repeat_ngram`` as in _slot_decode.  The Beam objects are filled as beam_search leaves them
-    (hypotheses, completed_hypotheses in append order, steps)."""
+    (hypotheses, completed_hypotheses in append order, steps).
+    ``groups`` / ``diversity`` other than (1, 0.0): diverse beam search (the rule of csrc/diverse_kernels.h, GroupBeam on the host) --
+    the k slots of a graph are ``groups`` groups of k // groups, slot 0 of every group live at step 0, per-group state, and the
+    advance and the reorder of a step are gtos_diverse_advance / gtos_diverse_reorder; a beam then holds what gather_groups leaves.
+    ``grouped`` = True takes that route whatever the two settings are (groups = 1 must give the plain search's beams)."""
+    if grouped is None:
+        grouped = groups != 1 or diversity != 0.0
+    if grouped:
+        return _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, groups, float(diversity))
+
     def layout(d):
         return ([('state', (d.B, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
                  ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0)], [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0)])
@@ -245,6 +343,34 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat
                         lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]))
 
 
+def _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, G, diversity):
+    """The grouped route of beam_search_device: the same launch sequence per step (one top-k over the whole k, one advance, one
+    reorder, the n-gram kernel when asked -- parents are global slot indices, so it works as it is) and the same host reads."""
+    if beams:
+        assert G >= 1 and beams[0].beam_size % G == 0 and 0 <= diversity < float('inf'), "groups divide the beam size; diversity is finite and >= 0"
+        g = beams[0].beam_size // G
+
+    def layout(d):
+        return ([('state', (d.B * G, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
+                 ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0)], [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0)])
+
+    def step(d, t, ll, cur, nxt, tok_out, char_out):
+        a, tab = d.arr, d.tab
+        topv, topi = ops.beam_topk(ll, d.k)
+        ops.diverse_advance(t, d.k, G, diversity, d.V, d.tot, d.min_t, d.max_t, topv, topi, tab['flag_shared'], tab['flag_local'],
+                            a['slot_score'], a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'],
+                            a['active'])
+        ops.diverse_reorder(cur, nxt, t, d.k, g, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
+                            tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+    fill = lambda beams_, k, **tables: fill_beams(beams_, k, groups=G, **tables)
+    _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, (g, 1) if beams else 1, layout, step, fill,
+                 no_repeat_ngram, lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]))
+    for beam in beams:
+        if getattr(beam, 'groups', None) is None:            # no step ran (max_time_step <= 0): fresh groups
+            gather_groups(beam, [Beam(g, beam.min_time_step, beam.max_time_step) for _ in range(G)])
+    return beams
+
+
 def slot_memory(memory, B, k):
     """The graph memory of Generator.work (B graphs) gathered once per fixed slot: slot s reads graph s // k."""
     graph_of = torch.arange(B * k, device=memory['probe'].device) // k
@@ -254,15 +380,19 @@ def slot_memory(memory, B, k):
             'inf_ext_kv': [sel(v) for v in memory['inf_ext_kv']], 'align_kv': sel(memory['align_kv'])}
 
 
-def fill_beams(beams, k, state, bp_parent, bp_token, comp_step, comp_parent, slot_score, comp_score, token_string):
+def fill_beams(beams, k, state, bp_parent, bp_token, comp_step, comp_parent, slot_score, comp_score, token_string, groups=None):
     """The Beam objects of a fixed-slot search from its tables (flat lists): state [B*4] (steps, #completed, #live, done),
     bp_parent / bp_token [T*N] (row t: parent slot and token id of every slot after step t), comp_step / comp_parent / comp_score
-    [B*k] (completions in append order), slot_score [N]; token_string(b, id) -> the string of an output id of graph b."""
+    [B*k] (completions in append order), slot_score [N]; token_string(b, id) -> the string of an output id of graph b.
+    ``groups`` = G (a grouped search, state [B*G*4]): beam b is gather_groups over G Beam objects of width k // G, group j filled from
+    state row b*G + j, slots and completion rows b*k + j*(k // G) onwards."""
     N = len(beams) * k
-    for b, beam in enumerate(beams):
-        steps, ncomp, nlive = state[4 * b:4 * b + 3]
+
+    def fill(beam, b, q, width):
+        """``beam`` (width ``width``) of graph b from state row q, slots and completion rows q*width onwards"""
+        steps, ncomp, nlive = state[4 * q:4 * q + 3]
         if steps == 0:
-            continue
+            return
 
         def seq_of(slot, tl):
             ids = []
@@ -271,10 +401,19 @@ def fill_beams(beams, k, state, bp_parent, bp_token, comp_step, comp_parent, slo
                 slot = bp_parent[tl * N + slot]
                 tl -= 1
             return [STR] + [token_string(b, i) for i in reversed(ids)]
-        beam.completed_hypotheses = [Hypothesis(seq_of(comp_parent[b * k + j], comp_step[b * k + j] - 1) + [END], comp_score[b * k + j])
+        at = q * width
+        beam.completed_hypotheses = [Hypothesis(seq_of(comp_parent[at + j], comp_step[at + j] - 1) + [END], comp_score[at + j])
                                      for j in range(ncomp)]
-        beam.hypotheses = [Hypothesis(seq_of(b * k + j, steps - 1), slot_score[b * k + j]) for j in range(nlive)]
+        beam.hypotheses = [Hypothesis(seq_of(at + j, steps - 1), slot_score[at + j]) for j in range(nlive)]
         beam.steps = steps
+    for b, beam in enumerate(beams):
+        if groups is None:
+            fill(beam, b, b, k)
+        else:
+            subs = [Beam(k // groups, beam.min_time_step, beam.max_time_step) for _ in range(groups)]
+            for j, sub in enumerate(subs):
+                fill(sub, b, b * groups + j, k // groups)
+            gather_groups(beam, subs)
     return beams
 
 

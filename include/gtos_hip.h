@@ -498,6 +498,32 @@ int gtos_sample_step(int N, int k, int t, int V, int tot, int min_time_step, int
 int gtos_ngram_block(int N, int k, int t, int max_time_step, int n, int tot, float* ll, int64_t ld, const int* parent,
                      const int* token, const int* hist_prev, int* hist_cur, const int* active, void* stream);
 
+/* ---- Diverse (group) beam search on the device (ABI 27; csrc/diverse.hip, the rule in csrc/diverse_kernels.h), driven by
+ * gtos_amd.search.beam_search_device(groups=, diversity=): group beam search with a Hamming diversity penalty (Vijayakumar et al.,
+ * "Diverse Beam Search").  The k slots of a graph are cut into `groups` groups of width g = k / groups; group j of graph b is group
+ * q = b * groups + j, owns slots q*g .. q*g + g - 1 and is a width-g beam of its own: group_state int32 [B*groups, 4] and the rows
+ * q*g .. of comp_step / comp_parent / comp_score (the [B,k] tables of gtos_beam_advance read as [B, groups, g]).  The rule has no
+ * counterpart in generator/search.py.  The top-k pass is gtos_beam_topk(ll, k).
+ * _advance (one workgroup per graph, step t < max_time_step) takes the graph's groups in order with a list of chosen output ids,
+ *   empty at first: a group pools the k candidates of each of its live slots, sorts them (stable, descending) by
+ *   model score - diversity * (occurrences of the candidate's id in the list), cuts to g - #completed and places the cut as
+ *   gtos_beam_advance does; the ids of the surviving entries join the list.  Every score written (slot_score, comp_score) is the model
+ *   score.  diversity_bits is the bit pattern of the fp64 penalty weight.  groups = 1 leaves exactly the tables of gtos_beam_advance.
+ *   active as there: the flag is "some not-done group has a live slot".
+ *   SHAPES (-10 outside): 1 <= k <= 32, groups >= 1, k % groups == 0, the penalty finite and >= 0, 0 <= t < max_time_step,
+ *   1 <= V <= tot; -23 for a null pointer (flag_local may be null when tot == V).
+ * _reorder: gtos_beam_reorder with the liveness of slot s read from group_state[s / g] (g = the group width, k % g == 0); the copy
+ *   tables are still those of graph s / k.  g = k is gtos_beam_reorder. */
+int gtos_diverse_advance(int B, int k, int groups, uint64_t diversity_bits, int t, int V, int tot, int min_time_step,
+                         int max_time_step, const float* topv, const int* topi, const uint8_t* flag_shared,
+                         const uint8_t* flag_local, double* slot_score, int* group_state, int* bp_parent, int* bp_token,
+                         int* comp_step, int* comp_parent, double* comp_score, int* active, void* stream);
+int gtos_diverse_reorder(int n_caches, void* const* src, void* const* dst, int64_t row_bytes, int N, int k, int g, int t,
+                         int max_time_step, const int* bp_parent, const int* bp_token, const int* group_state,
+                         const int* active, int V, int tot, const int64_t* tok_shared, const int64_t* tok_local,
+                         const int64_t* char_shared, const int64_t* char_local, int C, int64_t dead_tok,
+                         const int64_t* dead_char, int64_t* tok_out, int64_t* char_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
