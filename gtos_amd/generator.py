@@ -70,6 +70,40 @@ def check_groups(groups, diversity, beam_size, search):
     return int(groups), float(diversity)
 
 
+def check_constraints(constraints, search, groups, local_idx2token, vocab):
+    """The argument checks of Generator.work(constraints=): None passes as None.  Otherwise ValueError unless the search is a beam
+    search without groups and ``constraints`` holds, per graph of ``local_idx2token`` (the batch's copy tables), a list of at most
+    ops.CONSTRAIN_MAX distinct token strings, none of them <PAD>, <STR>, <END> or <UNK>, each producible for its graph: one of the
+    graph's copy tokens, or a word of ``vocab`` (the predictable-token vocabulary) with an id of its own.  -> a list of lists."""
+    if constraints is None:
+        return None
+    if search == "sample":
+        raise ValueError("constraints apply to the beam searches, not to search='sample'")
+    if groups != 1:
+        raise ValueError("constraints do not combine with groups (got groups = %r)" % (groups,))
+    if isinstance(constraints, str) or not isinstance(constraints, (list, tuple)) or len(constraints) != len(local_idx2token):
+        raise ValueError("constraints holds one list of token strings per graph: %d graphs, got %r"
+                         % (len(local_idx2token), constraints if not isinstance(constraints, (list, tuple)) else len(constraints)))
+    out = []
+    for b, (words, local) in enumerate(zip(constraints, local_idx2token)):
+        if isinstance(words, str) or not isinstance(words, (list, tuple)):
+            raise ValueError("constraints[%d] is a list of token strings, got %r" % (b, words))
+        if len(words) > ops.CONSTRAIN_MAX:
+            raise ValueError("constraints[%d]: at most %d constraints per graph, got %d" % (b, ops.CONSTRAIN_MAX, len(words)))
+        copies = set(local.values())
+        for w in words:
+            if not isinstance(w, str):
+                raise ValueError("constraints[%d]: a constraint is a token string, got %r" % (b, w))
+            if w in (PAD, STR, END, UNK):
+                raise ValueError("constraints[%d]: %s cannot be a constraint" % (b, w))
+            if w not in copies and vocab.token2idx(w) == vocab.unk_idx:
+                raise ValueError("constraints[%d]: %r is neither a copy token of the graph nor in the vocabulary" % (b, w))
+        if len(set(words)) != len(words):
+            raise ValueError("constraints[%d]: constraints are a set of single tokens, got a duplicate in %r" % (b, list(words)))
+        out.append(list(words))
+    return out
+
+
 class Scores(collections.namedtuple("Scores", "sentence_ll tokens correct token_ll pred graph_of")):
     """What Generator.score returns, all DEVICE tensors over N scored sequences of at most T target positions (tokens + <END>):
     sentence_ll [N] fp64 = log p(sequence | graph), tokens [N] int32 (target positions), correct [N] int32 (positions whose argmax
@@ -203,7 +237,7 @@ class Generator(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ inference
     def work(self, data, beam_size, max_time_step, min_time_step=1, search="host", *, temperature=1.0, top_k=0, top_p=1.0,
-             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0):
+             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
         step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
@@ -215,11 +249,18 @@ class Generator(nn.Module):
         beam_size / G that search one after the other, a group's selection lowering every candidate by ``diversity`` for each
         hypothesis of the groups before it that took the same token at this step (gtos_amd.search.GroupBeam, the rule of
         csrc/diverse_kernels.h; on the device by gtos_diverse_advance / gtos_diverse_reorder).  Scores stay log-likelihoods.  A
-        returned beam then carries ``groups``, G Beam objects of width beam_size / G, and its own lists are theirs in group order."""
+        returned beam then carries ``groups``, G Beam objects of width beam_size / G, and its own lists are theirs in group order.
+        ``constraints`` ("host" and "device", groups = 1): one list of token strings per graph (a list may be empty) that its output
+        must hold -- lexically constrained beam search with dynamic beam allocation (gtos_amd.search.ConstrainedBeam, the rule of
+        csrc/constrain_kernels.h; on the device by gtos_constrain_advance).  A string is one of the graph's copy tokens
+        (``data['local_idx2token']``) or a vocabulary word; a hypothesis ends only when it holds them all; scores stay
+        log-likelihoods (check_constraints).  A returned beam then carries ``met``, the constraint bit masks of its live hypotheses."""
         if search not in ("host", "device", "sample"):
             raise ValueError("search must be 'host', 'device' or 'sample', got %r" % (search,))
         no_repeat_ngram = check_no_repeat_ngram(no_repeat_ngram, search, max_time_step)
         groups, diversity = check_groups(groups, diversity, beam_size, search)
+        if constraints is not None:
+            constraints = check_constraints(constraints, search, groups, data['local_idx2token'], self.vocabs['predictable_token'])
         if search == "sample":
             check_sampling(beam_size, temperature, top_k, top_p, seed)
             if seed is None:
@@ -245,6 +286,8 @@ class Generator(nn.Module):
             block = dict(no_repeat_ngram=no_repeat_ngram) if no_repeat_ngram else {}       # n = 0: the calls as they always were
             if groups != 1:                                                                # groups = 1: likewise
                 block.update(groups=groups, diversity=diversity)
+            if constraints is not None:                                                    # None: likewise
+                block.update(constraints=constraints)
             if search == "device":
                 beam_search_device(self, memory, beams, **block)
             elif search == "sample":
@@ -438,12 +481,13 @@ class Generator(nn.Module):
         token_char = torch.tensor([rows], dtype=torch.int64)
         return token.to(self.device), token_char.to(self.device)
 
-    def decode_step_batched(self, tokens, state, memory, beam_of_hyp, offset, topk, banned=None):
+    def decode_step_batched(self, tokens, state, memory, beam_of_hyp, offset, topk, banned=None, want=None):
         """One step for N live hypotheses of ALL beams (what gtos_amd.search.beam_search drives).  tokens: their last token
         strings; state: None or {'snt': [cache per sentence-encoder layer], 'inf': [cache per inference layer]}, every cache
         [t,N,2d]; memory: per GRAPH (``work``); beam_of_hyp [N]: graph index of each hypothesis; banned: None or per hypothesis the output
         ids whose ll is -inf before the top-k (search.banned_tokens).  Returns (state grown by one row, per hypothesis the top-k
-        [(token string, log-likelihood)])."""
+        [(token string, log-likelihood)]); with ``want`` (per hypothesis a list of output ids) a third value: per hypothesis the
+        log-likelihoods of those ids after the banning."""
         inp = self.prepare_incremental_input([[t] for t in tokens])
         sel = lambda v: v.index_select(1, beam_of_hyp)
         owners = beam_of_hyp.tolist()
@@ -451,9 +495,9 @@ class Generator(nn.Module):
                'tot_ext': memory['tot_ext'], 'inf_ext_kv': [sel(v) for v in memory['inf_ext_kv']],
                'snt_ext_kv': [sel(v) for v in memory['snt_ext_kv']], 'align_kv': sel(memory['align_kv']),
                'local_idx2token': [memory['local_idx2token'][bi] for bi in owners]}
-        snt, inf, results = self._decode_core(inp, None if state is None else state['snt'], None if state is None else state['inf'],
-                                              mem, offset, topk, banned)
-        return {'snt': snt, 'inf': inf}, results
+        snt, inf, results, *lls = self._decode_core(inp, None if state is None else state['snt'], None if state is None else state['inf'],
+                                                    mem, offset, topk, banned, want)
+        return ({'snt': snt, 'inf': inf}, results, *lls)
 
     def _step_embed(self, inp, offset):
         step_token, step_token_char = inp
@@ -462,10 +506,10 @@ class Generator(nn.Module):
         ln = self.token_embed_layer_norm
         return ops.layer_norm_residual(x, None, ln.weight, ln.bias, 0.0, ln.eps)
 
-    def _decode_core(self, inp, snt_state, inf_state, mem, offset, topk, banned=None):
+    def _decode_core(self, inp, snt_state, inf_state, mem, offset, topk, banned=None, want=None):
         """inp = (step_token [1,N], step_token_char [1,N,C]); snt_state / inf_state: per layer [t,N,2d] or None; mem: everything
-        already per hypothesis; banned: None or per hypothesis the output ids that score -inf.  -> (new sentence-encoder caches, new
-        inference caches, top-k results)."""
+        already per hypothesis; banned: None or per hypothesis the output ids that score -inf; want: None or per hypothesis output ids
+        whose ll (after the banning) is returned too.  -> (new sentence-encoder caches, new inference caches, top-k results[, wanted lls])."""
         x = self._step_embed(inp, offset)
         snt_caches = []
         for li, layer in enumerate(self.snt_encoder.layers):
@@ -483,6 +527,12 @@ class Generator(nn.Module):
         results = []
         for s, t, local in zip(topk_scores.tolist(), topk_token.tolist(), mem['local_idx2token']):
             results.append([(local[i] if i in local else vocab.idx2token(i), sc) for sc, i in zip(s, t)])
+        if want is not None:
+            rows = [h for h, ids in enumerate(want) for _ in ids]
+            cols = [i for ids in want for i in ids]
+            flat = ll[torch.tensor(rows, dtype=torch.int64, device=ll.device), torch.tensor(cols, dtype=torch.int64, device=ll.device)].tolist() if rows else []
+            at = iter(flat)
+            return snt_caches, inf_caches, results, [[next(at) for _ in ids] for ids in want]
         return snt_caches, inf_caches, results
 
     # ---- the reference's decoding interface (generator/generator.py:96-167, generator/search.py:113-166)

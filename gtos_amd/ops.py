@@ -1377,6 +1377,37 @@ def diverse_advance(t, k, groups, diversity, V, tot, min_time_step, max_time_ste
          ptr(comp_score), ptr(active), stream())
 
 
+CONSTRAIN_MAX = 16       # MAX_CONS of csrc/constrain_kernels.h: the constraints one graph may carry (one bit of a slot's mask each)
+
+
+def constrain_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, ll, cons, flag_shared, flag_local, slot_score, beam_state,
+                      bp_parent, bp_token, comp_step, comp_parent, comp_score, met, active):
+    """One advance of every beam at step t under lexical constraints (gtos_constrain_advance, the rule of csrc/constrain_kernels.h):
+    beam_advance with ll [N, tot] fp32 (unit column stride; read for the forced candidates), cons int32 [B, Cw] (each graph's constraint
+    ids, then -1; Cw <= CONSTRAIN_MAX, 0 allowed) and met int32 [2, N] (the slots' masks, rows alternating by step parity); the other
+    tables as there."""
+    B = beam_state.shape[0]
+    N = B * k
+    require_cuda(topv, topi, ll, cons, flag_shared, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, met, active)
+    if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1 or ll.shape != (N, tot):
+        raise _lib.GtosHipError("constrain_advance: ll must be an [N, tot] fp32 tensor with unit column stride")
+    assert cons.dim() == 2 and cons.shape[0] == B and cons.shape[1] <= CONSTRAIN_MAX and cons.dtype == torch.int32
+    Cw = cons.shape[1]
+    assert met.shape == (2, N) and met.dtype == torch.int32
+    assert topv.shape == (N, k) and topi.shape == (N, k) and topv.dtype == torch.float32 and topi.dtype == torch.int32
+    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
+    assert flag_local is None or (flag_local.dtype == torch.uint8 and flag_local.numel() >= B * (tot - V))
+    assert slot_score.dtype == torch.float64 and slot_score.numel() == N and beam_state.shape == (B, 4) and beam_state.dtype == torch.int32
+    assert bp_parent.shape == (max_time_step, N) and bp_token.shape == (max_time_step, N)
+    assert comp_step.shape == (B, k) and comp_parent.shape == (B, k) and comp_score.shape == (B, k) and active.numel() == 3
+    for x in (topv, topi, cons, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, met,
+              active):
+        assert x is None or x.is_contiguous()
+    call("gtos_constrain_advance", B, k, Cw, t, V, tot, min_time_step, max_time_step, ptr(topv), ptr(topi), ptr(ll), max(ll.stride(0), tot),
+         ptr(cons) if Cw else None, ptr(flag_shared), ptr(flag_local), ptr(slot_score), ptr(beam_state), ptr(bp_parent), ptr(bp_token),
+         ptr(comp_step), ptr(comp_parent), ptr(comp_score), ptr(met), ptr(active), stream())
+
+
 def _check_next_input(N, k, V, tot, tok_shared, tok_local, char_shared, char_local, dead_char, tok_out, char_out):
     """The next-input table group of beam_reorder / sample_step (NextInput in csrc/slot_device.h): int64, contiguous, sized for N
     slots of k per graph, ids [0, V) shared and [V, tot) per graph, C characters.  -> C"""

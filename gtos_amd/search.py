@@ -20,6 +20,9 @@ flag every ``sync_every`` steps and the back-pointer / completion tables once at
 rule in csrc/diverse_kernels.h): the k hypotheses of a sentence are cut into groups that search one after the other, each steered away
 from the tokens the groups before it took at the same step.
 
+``constraints`` turn either beam search into lexically constrained beam search with dynamic beam allocation (ConstrainedBeam; on the
+device csrc/constrain.hip, the rule in csrc/constrain_kernels.h): tokens every finished hypothesis of a graph must hold.
+
 ``sample_device`` decodes by sampling instead (csrc/sample.hip): the same fixed slots, one independent sample per slot with
 temperature / top-k / top-p, and Beam objects filled the same way.
 """
@@ -160,6 +163,80 @@ def gather_groups(beam, groups):
     return beam
 
 
+class ConstrainedBeam(Beam):
+    """Lexically constrained beam search of one sentence with dynamic beam allocation (Post & Vilar 2018, single-token constraints):
+    the rule of csrc/constrain_kernels.h in Python.  ``constraints``: distinct token strings every finished hypothesis must hold;
+    ``met[h]``: the bit mask of those live hypothesis h has produced.  A step pools, per live hypothesis in order, its top-k candidates
+    -- an <END> only when the hypothesis holds every constraint -- and then, per constraint in order, a forced candidate when the
+    hypothesis lacks it, it is not among the top-k tokens and its log-likelihood is above -inf.  A candidate's bank is the number of
+    constraints it would hold.  Within a bank candidates rank by score (stable, descending); the pool is ordered by that rank, then by
+    bank, fullest first (the best of every bank, then the second best of every bank, ...), and cut and placed as Beam.advance does.
+    Without constraints this is Beam."""
+
+    def __init__(self, beam_size, min_time_step, max_time_step, constraints):
+        super().__init__(beam_size, min_time_step, max_time_step)
+        self.constraints = list(constraints)
+        assert len(set(self.constraints)) == len(self.constraints), "constraints are a set of single tokens"
+        self.met = [0]
+
+    def advance(self, last_steps, forced):
+        """last_steps as in Beam.advance; forced[h] = [(token, log-likelihood), ...], one entry per constraint in constraint order
+        (the log-likelihood as the selection sees it, after repeat-n-gram blocking) for live hypothesis h; which of them enter the pool
+        is decided here.  Returns the parents like Beam.advance."""
+        full = (1 << len(self.constraints)) - 1
+        bit = {w: 1 << i for i, w in enumerate(self.constraints)}
+        pool = []                                                       # (parent, token, score, mask), in pool position order
+        for parent, (steps, want) in enumerate(zip(last_steps, forced)):
+            base, met = self.hypotheses[parent].score, self.met[parent]
+            for token, ll in steps:
+                if token == END and met != full:
+                    continue
+                pool.append((parent, token, float('-inf') if token == UNK else base + ll, met | bit.get(token, 0)))
+            top = [token for token, _ in steps]
+            for i, (token, ll) in enumerate(want):
+                if (met >> i) & 1 or token in top or not ll > float('-inf'):
+                    continue
+                pool.append((parent, token, float('-inf') if token == UNK else base + ll, met | (1 << i)))
+        banks = {}
+        for c in pool:
+            banks.setdefault(bin(c[3]).count("1"), []).append(c)
+        ranked = []
+        for bank, cands in banks.items():
+            cands.sort(key=lambda c: c[2], reverse=True)                # stable: ties keep pool order
+            ranked.extend((q, -bank, c) for q, c in enumerate(cands))
+        ranked.sort(key=lambda x: x[:2])                                # (q, bank) is unique
+        alive, parents, met = [], [], []
+        for _, _, (parent, token, score, mask) in ranked[:self.beam_size - len(self.completed_hypotheses)]:
+            hyp = Hypothesis(self.hypotheses[parent].seq + [token], score)
+            if hyp.is_completed():
+                if len(hyp) - 2 >= self.min_time_step:
+                    self.completed_hypotheses.append(hyp)
+            else:
+                alive.append(hyp)
+                parents.append(parent)
+                met.append(mask)
+        self.hypotheses, self.met = alive, met
+        self.steps += 1
+        return parents
+
+
+def constraints_met(seq, constraints):
+    """How many distinct strings of ``constraints`` occur in ``seq`` (a list of token strings, e.g. Hypothesis.seq)."""
+    have = set(seq)
+    return sum(1 for w in set(constraints) if w in have)
+
+
+def constraint_ids(model, local_idx2token, constraints):
+    """Per graph the output ids of its constraint strings, by the convention of the n-gram code: the graph's copy id first, else the
+    predictable-token vocabulary's id."""
+    pv = model.vocabs['predictable_token']
+    out = []
+    for local, words in zip(local_idx2token, constraints):
+        copy_id = {w: i for i, w in local.items()}
+        out.append([copy_id[w] if w in copy_id else pv.token2idx(w) for w in words])
+    return out
+
+
 def banned_tokens(y, n):
     """The rule of csrc/ngram_kernels.h on a Python list: the tokens that would complete a repeated n-gram of y (n >= 1; n = 1: all of
     y), in position order, repeats included."""
@@ -168,17 +245,25 @@ def banned_tokens(y, n):
     return [y[i + n - 1] for i in range(t - n + 1) if y[i:i + n - 1] == suffix]
 
 
-def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0):
+def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None):
     """Runs all beams to completion.  ``model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, topk)`` ->
     (state, results); ``state`` is opaque here except that every tensor in it has the hypothesis axis at dim 1.  With
     ``no_repeat_ngram`` = n > 0 the call also gets, per hypothesis, the output ids that would repeat an n-gram of its tokens
     (banned_tokens on the strings after <STR>; string and id map one to one within a graph), which then score -inf.
     ``groups`` / ``diversity`` other than (1, 0.0): diverse beam search -- every (fresh) beam is searched as a GroupBeam of its
-    settings and then holds that search's result (gather_groups)."""
+    settings and then holds that search's result (gather_groups).
+    ``constraints`` (one list of token strings per graph, not with groups): lexically constrained search -- every (fresh) beam is
+    searched as a ConstrainedBeam and then holds that search's lists, steps and ``met``; the decode call also gets ``want``, per
+    hypothesis the output ids of its graph's constraints, and returns their log-likelihoods after banning."""
     device = memory['probe'].device
     state = None
     result = beams
-    if groups != 1 or diversity != 0.0:
+    if constraints is not None:
+        assert groups == 1 and diversity == 0.0 and len(constraints) == len(beams), "constraints: one list per graph, no groups"
+        beams = [ConstrainedBeam(b.beam_size, b.min_time_step, b.max_time_step, c) for b, c in zip(beams, constraints)]
+        cons_id = constraint_ids(model, memory['local_idx2token'], constraints)
+        live = lambda beam: beam.hypotheses
+    elif groups != 1 or diversity != 0.0:
         beams = [GroupBeam(b.beam_size, b.min_time_step, b.max_time_step, groups, diversity) for b in beams]
         live = GroupBeam.live_hypotheses
     else:
@@ -188,6 +273,7 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
         copy_id = [{w: i for i, w in local.items()} for local in memory['local_idx2token']]
     while True:
         owners, tokens, banned = [], [], []
+        forced = None
         for bi, beam in enumerate(beams):
             if not beam.completed():
                 for hyp in live(beam):
@@ -200,7 +286,11 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
         if not owners:
             break
         beam_of_hyp = torch.tensor(owners, dtype=torch.int64, device=device)
-        if no_repeat_ngram:
+        if constraints is not None:
+            state, results, lls = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size,
+                                                            banned if no_repeat_ngram else None, want=[cons_id[bi] for bi in owners])
+            forced = [list(zip(constraints[bi], row)) for bi, row in zip(owners, lls)]
+        elif no_repeat_ngram:
             state, results = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size, banned)
         else:
             state, results = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size)
@@ -210,7 +300,7 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
             if beam.completed():
                 continue
             n = len(live(beam))
-            parents = beam.advance(results[pos:pos + n])
+            parents = beam.advance(results[pos:pos + n]) if forced is None else beam.advance(results[pos:pos + n], forced[pos:pos + n])
             if not beam.completed():
                 keep.extend(pos + p for p in parents)
             pos += n
@@ -220,7 +310,10 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
         state = {k: [c.index_select(1, idx) for c in v] for k, v in state.items()}
     if result is not beams:
         for beam, run in zip(result, beams):
-            gather_groups(beam, run.groups)
+            if constraints is not None:
+                beam.hypotheses, beam.completed_hypotheses, beam.steps, beam.met = run.hypotheses, run.completed_hypotheses, run.steps, run.met
+            else:
+                gather_groups(beam, run.groups)
     return result
 
 
@@ -312,7 +405,8 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     return fill(beams, k, token_string=lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i), **host)
 
 
-def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0, groups=1, diversity=0.0, grouped=None):
+def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0, groups=1, diversity=0.0, grouped=None,
+                       constraints=None, constrained=None):
     """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
     decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
     steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
@@ -322,9 +416,19 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat
     ``groups`` / ``diversity`` other than (1, 0.0): diverse beam search (the rule of csrc/diverse_kernels.h, GroupBeam on the host) --
     the k slots of a graph are ``groups`` groups of k // groups, slot 0 of every group live at step 0, per-group state, and the
     advance and the reorder of a step are gtos_diverse_advance / gtos_diverse_reorder; a beam then holds what gather_groups leaves.
-    ``grouped`` = True takes that route whatever the two settings are (groups = 1 must give the plain search's beams)."""
+    ``grouped`` = True takes that route whatever the two settings are (groups = 1 must give the plain search's beams).
+    ``constraints`` (one list of token strings per graph, not with groups): lexically constrained search (the rule of
+    csrc/constrain_kernels.h, ConstrainedBeam on the host) -- the plain tables plus the slots' masks ``met`` and the constraint ids, a
+    step's advance being gtos_constrain_advance between the plain top-k and the plain reorder; a beam then also carries ``met``, the
+    masks of its live hypotheses.  ``constrained`` = True takes that route even without constraints (it must give the plain search's
+    beams)."""
     if grouped is None:
         grouped = groups != 1 or diversity != 0.0
+    if constrained is None:
+        constrained = constraints is not None
+    if constrained:
+        assert not grouped, "constraints do not combine with groups"
+        return _constrained_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, constraints)
     if grouped:
         return _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, groups, float(diversity))
 
@@ -368,6 +472,47 @@ def _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngra
     for beam in beams:
         if getattr(beam, 'groups', None) is None:            # no step ran (max_time_step <= 0): fresh groups
             gather_groups(beam, [Beam(g, beam.min_time_step, beam.max_time_step) for _ in range(G)])
+    return beams
+
+
+def _constrained_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, constraints):
+    """The constrained route of beam_search_device: the plain launch sequence per step with gtos_constrain_advance as the advance (it
+    reads ll after the n-gram kernel, so a banned constraint is not forced) and the same host reads."""
+    if constraints is None:
+        constraints = [[] for _ in beams]
+    assert len(constraints) == len(beams), "constraints: one list per graph"
+
+    def layout(d):
+        ids = constraint_ids(model, d.local, constraints)
+        width = max([len(x) for x in ids] + [0])
+        if width > ops.CONSTRAIN_MAX or any(not 0 <= i < d.tot for x in ids for i in x):
+            raise ValueError("constraints: at most %d per graph, each an output id of the batch" % ops.CONSTRAIN_MAX)
+        d.cons = torch.tensor([x + [-1] * (width - len(x)) for x in ids], dtype=torch.int32).view(d.B, width).to(memory['probe'].device)
+        return ([('state', (d.B, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
+                 ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0), ('met', (2, d.N), 0)],
+                [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0)])
+
+    def step(d, t, ll, cur, nxt, tok_out, char_out):
+        a, tab = d.arr, d.tab
+        topv, topi = ops.beam_topk(ll, d.k)
+        ops.constrain_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, topv, topi, ll, d.cons, tab['flag_shared'], tab['flag_local'],
+                              a['slot_score'], a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'],
+                              a['met'], a['active'])
+        ops.beam_reorder(cur, nxt, t, d.k, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
+                         tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+
+    def fill(beams_, k, met, state, **tables):
+        fill_beams(beams_, k, state=state, **tables)
+        N = len(beams_) * k
+        for b, beam in enumerate(beams_):                    # the row the beam's last advance wrote: step t writes row (t + 1) % 2
+            steps, nlive = state[4 * b], state[4 * b + 2]
+            beam.met = [met[(steps % 2) * N + b * k + j] for j in range(nlive)] if steps else [0]
+        return beams_
+    _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill, no_repeat_ngram,
+                 lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]))
+    for beam in beams:
+        if getattr(beam, 'met', None) is None:               # no step ran (max_time_step <= 0)
+            beam.met = [0]
     return beams
 
 

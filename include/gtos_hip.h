@@ -524,6 +524,28 @@ int gtos_diverse_reorder(int n_caches, void* const* src, void* const* dst, int64
                          const int64_t* char_shared, const int64_t* char_local, int C, int64_t dead_tok,
                          const int64_t* dead_char, int64_t* tok_out, int64_t* char_out, void* stream);
 
+/* ---- Lexically constrained beam search on the device (ABI 28; csrc/constrain.hip, the rule in csrc/constrain_kernels.h), driven by
+ * gtos_amd.search.beam_search_device(constraints=): single-token constraints with dynamic beam allocation (Post & Vilar, "Fast
+ * Lexically Constrained Decoding with Dynamic Beam Allocation").  cons int32 [B, Cw]: the output ids graph b must produce, distinct
+ * and of the plain class, then -1 (Cw <= 16; cons may be null when Cw == 0).  met int32 [2, N]: per slot the bit mask of its graph's
+ * constraints already produced, zero at the start; step t reads row t % 2 and writes row (t + 1) % 2.  The rule has no counterpart in
+ * generator/search.py.  The top-k pass is gtos_beam_topk(ll, k), the reorder gtos_beam_reorder: every other table is
+ * gtos_beam_advance's, in its format.
+ * _advance (one workgroup per graph, step t < max_time_step): gtos_beam_advance with a pool of k + Cw entries per live slot -- its k
+ *   candidates, of which an <END> is absent unless the slot holds every constraint, and per constraint i a forced candidate, present
+ *   when bit i of the slot's mask is clear, the id is not among the slot's k candidates and its ll (ll fp32 [N, tot], row stride ld,
+ *   as the selection sees it, i.e. after gtos_ngram_block) is above -inf, scored like a candidate.  An entry's bank is the number of
+ *   bits of the parent's mask plus its own constraint.  Within a bank entries rank by score (stable, descending, rank q); the final
+ *   order is ascending q, then descending bank; the cut is min(#present, k - #completed); the survivors' masks go to the new met row.
+ *   A graph without constraints gets exactly the tables of gtos_beam_advance.
+ *   SHAPES (-10 outside): 1 <= k <= 32, 0 <= Cw <= 16, 0 <= t < max_time_step, 1 <= V <= tot <= ld; -23 for a null pointer
+ *   (flag_local may be null when tot == V, cons when Cw == 0). */
+int gtos_constrain_advance(int B, int k, int Cw, int t, int V, int tot, int min_time_step, int max_time_step,
+                           const float* topv, const int* topi, const float* ll, int64_t ld, const int* cons,
+                           const uint8_t* flag_shared, const uint8_t* flag_local, double* slot_score, int* beam_state,
+                           int* bp_parent, int* bp_token, int* comp_step, int* comp_parent, double* comp_score, int* met,
+                           int* active, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
