@@ -49,7 +49,9 @@ class TokenGenerator(nn.Module):
             nn.init.constant_(l.bias, 0.)
 
     def forward(self, outs, graph_state, graph_padding_mask, copy_seq, target=None, work=False, align_kv=None,
-                tot_ext=None):
+                tot_ext=None, want_align=False):
+        """``want_align`` (with ``work``): -> (ll, align), align the contiguous fp32 [T,N,n] alignment weights the ll row was mixed from
+        (what the coverage penalty accumulates)."""
         p = self.dropout if self.training else 0.0
         cd = self.alignment_layer.compute_dtype
         outs_s, outs = ops.split_stream(outs, cd)      # (residual stream -- fp32 in bf16 mode --, GEMM operand)
@@ -70,6 +72,9 @@ class TokenGenerator(nn.Module):
         if work:
             if tot_ext is None:
                 tot_ext = 1 + int(copy_seq.max().item())
+            if want_align:
+                align = alignment_weight.float().contiguous()          # converted once: copy_log_likelihood takes it as it is
+                return ops.copy_log_likelihood(logits, div, align, copy_seq, tot_ext), align
             return ops.copy_log_likelihood(logits, div, alignment_weight, copy_seq, tot_ext)
         pad = self.vocabs['predictable_token'].padding_idx
         return ops.copy_nll(logits, div, alignment_weight, copy_seq, target, pad, self.label_smoothing).sum(0)
@@ -100,12 +105,12 @@ class DecodeLayer(nn.Module):
         self.dropout, self.vocabs = dropout, vocabs
 
     def forward(self, probe, graph_state, snt_state, graph_padding_mask, snt_padding_mask, attn_mask,
-                copy_seq, target=None, work=False):
+                copy_seq, target=None, work=False, want_align=False):
         outs = F.dropout(probe, p=self.dropout, training=self.training)
         outs = self.inference_core(outs, kv=snt_state, self_padding_mask=snt_padding_mask, self_attn_mask=attn_mask,
                                    external_memories=graph_state, external_padding_mask=graph_padding_mask)
         if work:
-            return self.token_generator(outs, graph_state, graph_padding_mask, copy_seq, work=True)
+            return self.token_generator(outs, graph_state, graph_padding_mask, copy_seq, work=True, want_align=want_align)
         token_loss = self.token_generator(outs, graph_state, graph_padding_mask, copy_seq, target=target, work=False)
         token_tot = snt_padding_mask.size(0) - snt_padding_mask.float().sum(0)
         return (token_loss / token_tot).mean()
@@ -117,26 +122,30 @@ class DecodeLayer(nn.Module):
                                    external_memories=graph_state, external_padding_mask=graph_padding_mask)
         return self.token_generator.evaluate(outs, graph_state, graph_padding_mask, copy_seq, target)
 
-    def step(self, probe, token_row, caches, mem):
+    def step(self, probe, token_row, caches, mem, want_align=False):
         """Log-likelihoods of the next token, [1,N,V+ext] (decoder.py:85-87 with work=True), for N live hypotheses.
         token_row [1,N,d]: the newest sentence-encoder state; caches: per inference layer [t,N,2d] or None;
-        mem: 'inf_ext_kv' (list), 'align_kv', 'graph_padding_mask', 'cp_seq', 'tot_ext' already gathered per hypothesis."""
+        mem: 'inf_ext_kv' (list), 'align_kv', 'graph_padding_mask', 'cp_seq', 'tot_ext' already gathered per hypothesis.
+        ``want_align``: the alignment weights [1,N,n] fp32 as an extra last return value."""
         outs = probe
         new_caches = []
         for li, layer in enumerate(self.inference_core.layers):
             outs, c = layer.step(outs, token_row, None if caches is None else caches[li], mem['inf_ext_kv'][li],
                                  mem['graph_padding_mask'])
             new_caches.append(c)
+        if want_align:
+            ll, align = self._step_ll(outs, mem, True)
+            return ll, new_caches, align
         return self._step_ll(outs, mem), new_caches
 
-    def step_into(self, probe, token_row, caches, t, mem):
+    def step_into(self, probe, token_row, caches, t, mem, want_align=False):
         """step() on preallocated caches (per inference layer [T_max,N,2d], row t written, rows [0,t] read; see
-        TransformerLayer.step_into).  Returns ll [1,N,V+ext]."""
+        TransformerLayer.step_into).  Returns ll [1,N,V+ext]; with ``want_align`` (ll, align [1,N,n] fp32)."""
         outs = probe
         for li, layer in enumerate(self.inference_core.layers):
             outs = layer.step_into(outs, token_row, caches[li], t, mem['inf_ext_kv'][li], mem['graph_padding_mask'])
-        return self._step_ll(outs, mem)
+        return self._step_ll(outs, mem, want_align)
 
-    def _step_ll(self, outs, mem):
+    def _step_ll(self, outs, mem, want_align=False):
         return self.token_generator(outs, None, mem['graph_padding_mask'], mem['cp_seq'], work=True,
-                                    align_kv=mem['align_kv'], tot_ext=mem['tot_ext'])
+                                    align_kv=mem['align_kv'], tot_ext=mem['tot_ext'], want_align=want_align)

@@ -22,7 +22,7 @@ from .encoder import TokenEncoder, RelationEncoder
 from .decoder import DecodeLayer
 from .transformer import Transformer, SinusoidalPositionalEmbedding, SelfAttentionMask
 from .graph_transformer import GraphTransformer, set_compute_dtype
-from .search import Beam, beam_search, beam_search_device, sample_device
+from .search import Beam, CoverageBeam, beam_search, beam_search_device, sample_device
 from .vocab import PAD, UNK, STR, END, lists_to_tensor, strings_to_char_tensor
 
 
@@ -102,6 +102,28 @@ def check_constraints(constraints, search, groups, local_idx2token, vocab):
             raise ValueError("constraints[%d]: constraints are a set of single tokens, got a duplicate in %r" % (b, list(words)))
         out.append(list(words))
     return out
+
+
+def check_coverage(beta, search, groups, constraints):
+    """The argument checks of Generator.work(coverage_penalty=): None passes as None.  Otherwise ValueError unless beta is a finite
+    real >= 0 (0.0: the plain search with the coverage reported) and the search is a beam search without groups or constraints."""
+    if beta is None:
+        return None
+    if isinstance(beta, bool) or not isinstance(beta, numbers.Real) or not 0 <= beta < math.inf:
+        raise ValueError("coverage_penalty must be a finite number >= 0 or None, got %r" % (beta,))
+    if search == "sample":
+        raise ValueError("coverage_penalty applies to the beam searches, not to search='sample'")
+    if groups != 1:
+        raise ValueError("coverage_penalty does not combine with groups (got groups = %r)" % (groups,))
+    if constraints is not None:
+        raise ValueError("coverage_penalty does not combine with constraints")
+    return float(beta)
+
+
+Coverage = collections.namedtuple("Coverage", "coverage cp tokens graph_of")
+Coverage.__doc__ = """What Generator.coverage returns, all DEVICE tensors over N sequences: coverage [N,n] fp32 (per graph node the
+alignment weight summed over the sequence's target positions, <END> included), cp [N] fp64 (the coverage penalty of that row: the sum
+over the nodes that are not padding of log(min(coverage, 1) + 1e-12)), tokens [N] int32 (target positions), graph_of [N] int64."""
 
 
 class Scores(collections.namedtuple("Scores", "sentence_ll tokens correct token_ll pred graph_of")):
@@ -237,7 +259,7 @@ class Generator(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ inference
     def work(self, data, beam_size, max_time_step, min_time_step=1, search="host", *, temperature=1.0, top_k=0, top_p=1.0,
-             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None):
+             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage_penalty=None):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
         step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
@@ -254,11 +276,18 @@ class Generator(nn.Module):
         must hold -- lexically constrained beam search with dynamic beam allocation (gtos_amd.search.ConstrainedBeam, the rule of
         csrc/constrain_kernels.h; on the device by gtos_constrain_advance).  A string is one of the graph's copy tokens
         (``data['local_idx2token']``) or a vocabulary word; a hypothesis ends only when it holds them all; scores stay
-        log-likelihoods (check_constraints).  A returned beam then carries ``met``, the constraint bit masks of its live hypotheses."""
+        log-likelihoods (check_constraints).  A returned beam then carries ``met``, the constraint bit masks of its live hypotheses.
+        ``coverage_penalty`` = beta >= 0 ("host" and "device", groups = 1, no constraints): the GNMT coverage penalty -- every
+        hypothesis accumulates the alignment weights of its steps over the graph nodes, and the selection ranks a candidate by its
+        log-likelihood plus beta * sum over the nodes of log(min(coverage, 1)) of its parent (gtos_amd.search.CoverageBeam, the rule of
+        csrc/coverage_kernels.h; on the device by gtos_coverage_step / gtos_coverage_advance).  Scores stay log-likelihoods.  The
+        returned beams are CoverageBeam objects -- ``get_k_best`` adds beta * cp to the length-normalised score -- of
+        CoveredHypothesis, each with ``cp`` and ``coverage`` (one float per node); 0.0 searches as without and reports them."""
         if search not in ("host", "device", "sample"):
             raise ValueError("search must be 'host', 'device' or 'sample', got %r" % (search,))
         no_repeat_ngram = check_no_repeat_ngram(no_repeat_ngram, search, max_time_step)
         groups, diversity = check_groups(groups, diversity, beam_size, search)
+        coverage_penalty = check_coverage(coverage_penalty, search, groups, constraints)
         if constraints is not None:
             constraints = check_constraints(constraints, search, groups, data['local_idx2token'], self.vocabs['predictable_token'])
         if search == "sample":
@@ -288,6 +317,9 @@ class Generator(nn.Module):
                 block.update(groups=groups, diversity=diversity)
             if constraints is not None:                                                    # None: likewise
                 block.update(constraints=constraints)
+            if coverage_penalty is not None:                                               # None: likewise
+                block.update(coverage=coverage_penalty)
+                beams = [CoverageBeam(beam_size, min_time_step, max_time_step, coverage_penalty) for _ in beams]
             if search == "device":
                 beam_search_device(self, memory, beams, **block)
             elif search == "sample":
@@ -342,10 +374,18 @@ class Generator(nn.Module):
                 m.training = was
 
     def _score_rows(self, data, given):
-        dev, pad = data['concept'].device, self.vocabs['predictable_token'].padding_idx
+        dev = data['concept'].device
         if given is not None and not given[0]:          # every n-best list empty: nothing to launch
             z = lambda dt: torch.zeros((0, 0), dtype=dt, device=dev)        # noqa: E731
             return z(torch.float32), z(torch.int32), z(torch.float32), z(torch.int64), torch.zeros(0, dtype=torch.int64, device=dev)
+        probe, concept_repr, token_repr, concept_mask, token_mask, attn_mask, cp_seq, target, graph_of = self._teacher_forced(data, given)
+        nll, pred, p_pred = self.decoder.evaluate(probe, concept_repr, token_repr, concept_mask, token_mask, attn_mask, cp_seq, target)
+        return nll, pred, p_pred, target, graph_of
+
+    def _teacher_forced(self, data, given):
+        """The full-sequence pass up to the decoder, for the batch's own sentences or ``given`` (_score_sequences): the decoder's
+        operands (probe, graph states, sentence states, their masks, the copy ids) per sequence, then target [T,N] and graph_of [N]."""
+        dev = data['concept'].device
         concept_repr, concept_mask, probe = self.encode_step(data, train=False)
         concept_repr, cp_seq = concept_repr.contiguous(), data['cp_seq']
         if given is None:
@@ -369,9 +409,7 @@ class Generator(nn.Module):
         token_repr = self.snt_encoder(token_repr, self_padding_mask=token_mask, self_attn_mask=attn_mask,
                                       external_memories=concept_repr, external_padding_mask=concept_mask)
         token_repr = ops.split_stream(token_repr, self.compute_dtype)[1]
-        nll, pred, p_pred = self.decoder.evaluate(probe.expand_as(token_repr), concept_repr, token_repr, concept_mask, token_mask,
-                                                  attn_mask, cp_seq.contiguous(), target)
-        return nll, pred, p_pred, target, graph_of
+        return probe.expand_as(token_repr), concept_repr, token_repr, concept_mask, token_mask, attn_mask, cp_seq.contiguous(), target, graph_of
 
     def score(self, data, targets=None):
         """Teacher-forced log-likelihoods: of the batch's own sentences (``data['token_out']`` given ``data['token_in']``), or of
@@ -386,6 +424,41 @@ class Generator(nn.Module):
                      correct=(pred.eq(target) & live).sum(0).to(torch.int32), token_ll=-nll, pred=pred, graph_of=graph_of)
         out.vocab = self.vocabs['predictable_token']
         return out
+
+    def coverage(self, data, targets=None):
+        """Teacher-forced coverage of the graph nodes, next to ``score`` and with its target handling: per sequence the alignment
+        weights of the full-sequence pass (the attention the copy mechanism reads) summed over its target positions, and the coverage
+        penalty of that row, by the kernel the searches use (gtos_coverage_step on a zero coverage).  A node whose coverage stays
+        near 0 was never verbalised.  Eval mode under no_grad, the module's mode left as found.  Returns ``Coverage``."""
+        given = None if targets is None else self._score_sequences(data, targets)
+        modes = [(m, m.training) for m in self.modules()]
+        enc = self.relation_encoder
+        trie_was = getattr(enc, "trie_in_eval", True)
+        try:
+            self.eval()
+            enc.trie_in_eval = False                    # as score_rows: the whole bank in one packed pass
+            with torch.no_grad():
+                return self._coverage(data, given)
+        finally:
+            enc.trie_in_eval = trie_was
+            for m, was in modes:
+                m.training = was
+
+    def _coverage(self, data, given):
+        dev = data['concept'].device
+        if given is not None and not given[0]:          # every n-best list empty: nothing to launch
+            n = max(data['concept'].size(0) - 1, 0)
+            return Coverage(torch.zeros((0, n), dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.float64, device=dev),
+                            torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev))
+        probe, concept_repr, token_repr, concept_mask, token_mask, attn_mask, cp_seq, target, graph_of = self._teacher_forced(data, given)
+        _, align = self.decoder(probe, concept_repr, token_repr, concept_mask, token_mask, attn_mask, cp_seq, work=True, want_align=True)
+        live = target.ne(self.vocabs['predictable_token'].padding_idx)
+        total = (align * live.unsqueeze(2).to(align.dtype)).sum(0).contiguous()                 # [N, n]
+        N = total.size(0)
+        cov, cp = torch.empty_like(total), torch.empty(N, dtype=torch.float64, device=dev)
+        ops.coverage_step(0, 1, total, concept_mask.contiguous(), None, torch.zeros_like(total), cov, cp,
+                          torch.ones(3, dtype=torch.int32, device=dev))
+        return Coverage(coverage=cov, cp=cp, tokens=live.sum(0).to(torch.int32), graph_of=graph_of)
 
     # ---- fixed-slot decoding for gtos_amd.search.beam_search_device
     def search_tables(self, local_idx2token, tot):
@@ -451,14 +524,17 @@ class Generator(nn.Module):
         return [[torch.zeros((max_time_step, N, 2 * self.embed_dim), dtype=l.self_attn.compute_dtype, device=self.device)
                  for _ in range(copies)] for l in layers]
 
-    def decode_slots(self, inp, caches, mem, t):
+    def decode_slots(self, inp, caches, mem, t, want_align=False):
         """Step t of the fixed-slot search: inp = (step_token [1,N], step_token_char [1,N,C]); caches: one [T_max,N,2d] buffer per
         sentence-encoder layer, then per inference layer (rows [0,t) hold the prefix, row t is written); mem: everything per slot.
-        -> ll [N, V+ext] fp32."""
+        -> ll [N, V+ext] fp32; with ``want_align`` (ll, align [N, n] fp32: the slots' alignment weights over the graph nodes)."""
         n_snt = len(self.snt_encoder.layers)
         x = self._step_embed(inp, t)
         for li, layer in enumerate(self.snt_encoder.layers):
             x = layer.step_into(x, x, caches[li], t, mem['snt_ext_kv'][li], mem['graph_padding_mask'])
+        if want_align:
+            ll, align = self.decoder.step_into(mem['probe'], x, caches[n_snt:], t, mem, want_align=True)
+            return ll[0], align[0]
         return self.decoder.step_into(mem['probe'], x, caches[n_snt:], t, mem)[0]
 
     def prepare_incremental_input(self, step_seq):
@@ -481,13 +557,13 @@ class Generator(nn.Module):
         token_char = torch.tensor([rows], dtype=torch.int64)
         return token.to(self.device), token_char.to(self.device)
 
-    def decode_step_batched(self, tokens, state, memory, beam_of_hyp, offset, topk, banned=None, want=None):
+    def decode_step_batched(self, tokens, state, memory, beam_of_hyp, offset, topk, banned=None, want=None, want_align=False):
         """One step for N live hypotheses of ALL beams (what gtos_amd.search.beam_search drives).  tokens: their last token
         strings; state: None or {'snt': [cache per sentence-encoder layer], 'inf': [cache per inference layer]}, every cache
         [t,N,2d]; memory: per GRAPH (``work``); beam_of_hyp [N]: graph index of each hypothesis; banned: None or per hypothesis the output
         ids whose ll is -inf before the top-k (search.banned_tokens).  Returns (state grown by one row, per hypothesis the top-k
         [(token string, log-likelihood)]); with ``want`` (per hypothesis a list of output ids) a third value: per hypothesis the
-        log-likelihoods of those ids after the banning."""
+        log-likelihoods of those ids after the banning; with ``want_align`` a last value: the alignment weights [N, n] fp32."""
         inp = self.prepare_incremental_input([[t] for t in tokens])
         sel = lambda v: v.index_select(1, beam_of_hyp)
         owners = beam_of_hyp.tolist()
@@ -496,7 +572,7 @@ class Generator(nn.Module):
                'snt_ext_kv': [sel(v) for v in memory['snt_ext_kv']], 'align_kv': sel(memory['align_kv']),
                'local_idx2token': [memory['local_idx2token'][bi] for bi in owners]}
         snt, inf, results, *lls = self._decode_core(inp, None if state is None else state['snt'], None if state is None else state['inf'],
-                                                    mem, offset, topk, banned, want)
+                                                    mem, offset, topk, banned, want, want_align)
         return ({'snt': snt, 'inf': inf}, results, *lls)
 
     def _step_embed(self, inp, offset):
@@ -506,16 +582,22 @@ class Generator(nn.Module):
         ln = self.token_embed_layer_norm
         return ops.layer_norm_residual(x, None, ln.weight, ln.bias, 0.0, ln.eps)
 
-    def _decode_core(self, inp, snt_state, inf_state, mem, offset, topk, banned=None, want=None):
+    def _decode_core(self, inp, snt_state, inf_state, mem, offset, topk, banned=None, want=None, want_align=False):
         """inp = (step_token [1,N], step_token_char [1,N,C]); snt_state / inf_state: per layer [t,N,2d] or None; mem: everything
         already per hypothesis; banned: None or per hypothesis the output ids that score -inf; want: None or per hypothesis output ids
-        whose ll (after the banning) is returned too.  -> (new sentence-encoder caches, new inference caches, top-k results[, wanted lls])."""
+        whose ll (after the banning) is returned too; want_align: the alignment weights [N, n] fp32 are returned last.
+        -> (new sentence-encoder caches, new inference caches, top-k results[, wanted lls][, align])."""
         x = self._step_embed(inp, offset)
         snt_caches = []
         for li, layer in enumerate(self.snt_encoder.layers):
             x, c = layer.step(x, x, None if snt_state is None else snt_state[li], mem['snt_ext_kv'][li], mem['graph_padding_mask'])
             snt_caches.append(c)
-        ll, inf_caches = self.decoder.step(mem['probe'], x, inf_state, mem)
+        if want_align:
+            ll, inf_caches, align = self.decoder.step(mem['probe'], x, inf_state, mem, want_align=True)
+            tail = (align.squeeze(0),)
+        else:
+            ll, inf_caches = self.decoder.step(mem['probe'], x, inf_state, mem)
+            tail = ()
         ll = ll.squeeze(0).float()
         if banned is not None and any(banned):
             rows = [h for h, ids in enumerate(banned) for _ in ids]
@@ -532,8 +614,8 @@ class Generator(nn.Module):
             cols = [i for ids in want for i in ids]
             flat = ll[torch.tensor(rows, dtype=torch.int64, device=ll.device), torch.tensor(cols, dtype=torch.int64, device=ll.device)].tolist() if rows else []
             at = iter(flat)
-            return snt_caches, inf_caches, results, [[next(at) for _ in ids] for ids in want]
-        return snt_caches, inf_caches, results
+            return (snt_caches, inf_caches, results, [[next(at) for _ in ids] for ids in want]) + tail
+        return (snt_caches, inf_caches, results) + tail
 
     # ---- the reference's decoding interface (generator/generator.py:96-167, generator/search.py:113-166)
     def reference_memory(self, data):

@@ -1408,6 +1408,58 @@ def constrain_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, ll
          ptr(comp_step), ptr(comp_parent), ptr(comp_score), ptr(met), ptr(active), stream())
 
 
+def coverage_step(t, k, align, pad, parent, cov_prev, cov_cur, cp, active):
+    """The coverage of the graph nodes and its penalty at step t (gtos_coverage_step, the rule of csrc/coverage_kernels.h):
+    cov_cur[s] = cov_prev[parent[s]] + align[s] (fp32 [N, n]; align: the alignment weights copy_log_likelihood consumes; parent int32
+    [N], None: a slot is its own parent, a negative entry: a dead slot, zero row) and cp[s] (fp64 [N]) = the sum over the nodes with
+    pad [n, N] (bool / uint8) clear of log(min(cov_cur, 1) + 1e-12).  The two coverage buffers alternate by step parity."""
+    require_cuda(align, pad, parent, cov_prev, cov_cur, cp, active)
+    if align.dim() != 2 or align.dtype != torch.float32 or not align.is_contiguous() or align.shape[1] < 1:
+        raise _lib.GtosHipError("coverage_step: align must be a contiguous [N, n] fp32 tensor with n >= 1")
+    N, n = align.shape
+    assert k >= 1 and N % k == 0 and t >= 0
+    assert pad.shape == (n, N) and pad.dtype in (torch.bool, torch.uint8)
+    assert cov_prev.shape == (N, n) and cov_cur.shape == (N, n) and cov_prev.dtype == torch.float32 and cov_cur.dtype == torch.float32
+    assert cov_prev.data_ptr() != cov_cur.data_ptr(), "coverage_step: the two coverage buffers alternate"
+    assert cp.dtype == torch.float64 and cp.numel() == N and active.numel() == 3 and active.dtype == torch.int32
+    assert parent is None or (parent.dtype == torch.int32 and parent.numel() == N)
+    for x in (pad, parent, cov_prev, cov_cur, cp, active):
+        assert x is None or x.is_contiguous()
+    call("gtos_coverage_step", N, k, t, n, ptr(align), ptr(pad), ptr(parent), ptr(cov_prev), ptr(cov_cur), ptr(cp), ptr(active), stream())
+
+
+def coverage_advance(t, k, beta, V, tot, min_time_step, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state,
+                     bp_parent, bp_token, comp_step, comp_parent, comp_score, cp, cov_cur, slot_cp, comp_cp, comp_cov, slot_cov, active):
+    """One advance of every beam at step t under the coverage penalty (gtos_coverage_advance, the rule of csrc/coverage_kernels.h):
+    beam_advance with the pool ranked by score + beta * cp[parent slot] (cp fp64 [N], cov_cur fp32 [N, n]: this step's
+    coverage_step), which also records per surviving slot slot_cp fp64 [N] / slot_cov fp32 [N, n] and per completion comp_cp fp64
+    [B, k] / comp_cov fp32 [B, k, n]; the other tables as there."""
+    import struct
+    B = beam_state.shape[0]
+    N = B * k
+    require_cuda(topv, topi, flag_shared, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, cp, cov_cur,
+                 slot_cp, comp_cp, comp_cov, slot_cov, active)
+    assert isinstance(beta, float) and 0 <= beta < float('inf')
+    assert cov_cur.dim() == 2 and cov_cur.shape[0] == N and cov_cur.shape[1] >= 1 and cov_cur.dtype == torch.float32
+    n = cov_cur.shape[1]
+    assert cp.dtype == torch.float64 and cp.numel() == N and slot_cp.dtype == torch.float64 and slot_cp.numel() == N
+    assert comp_cp.dtype == torch.float64 and comp_cp.shape == (B, k)
+    assert comp_cov.shape == (B, k, n) and comp_cov.dtype == torch.float32 and slot_cov.shape == (N, n) and slot_cov.dtype == torch.float32
+    assert topv.shape == (N, k) and topi.shape == (N, k) and topv.dtype == torch.float32 and topi.dtype == torch.int32
+    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
+    assert flag_local is None or (flag_local.dtype == torch.uint8 and flag_local.numel() >= B * (tot - V))
+    assert slot_score.dtype == torch.float64 and slot_score.numel() == N and beam_state.shape == (B, 4) and beam_state.dtype == torch.int32
+    assert bp_parent.shape == (max_time_step, N) and bp_token.shape == (max_time_step, N)
+    assert comp_step.shape == (B, k) and comp_parent.shape == (B, k) and comp_score.shape == (B, k) and active.numel() == 3
+    for x in (topv, topi, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, cp,
+              cov_cur, slot_cp, comp_cp, comp_cov, slot_cov, active):
+        assert x is None or x.is_contiguous()
+    bits = struct.unpack("<Q", struct.pack("<d", beta))[0]
+    call("gtos_coverage_advance", B, k, t, V, tot, min_time_step, max_time_step, bits, n, ptr(topv), ptr(topi), ptr(flag_shared),
+         ptr(flag_local), ptr(slot_score), ptr(beam_state), ptr(bp_parent), ptr(bp_token), ptr(comp_step), ptr(comp_parent),
+         ptr(comp_score), ptr(cp), ptr(cov_cur), ptr(slot_cp), ptr(comp_cp), ptr(comp_cov), ptr(slot_cov), ptr(active), stream())
+
+
 def _check_next_input(N, k, V, tot, tok_shared, tok_local, char_shared, char_local, dead_char, tok_out, char_out):
     """The next-input table group of beam_reorder / sample_step (NextInput in csrc/slot_device.h): int64, contiguous, sized for N
     slots of k per graph, ids [0, V) shared and [V, tot) per graph, C characters.  -> C"""

@@ -23,6 +23,10 @@ from the tokens the groups before it took at the same step.
 ``constraints`` turn either beam search into lexically constrained beam search with dynamic beam allocation (ConstrainedBeam; on the
 device csrc/constrain.hip, the rule in csrc/constrain_kernels.h): tokens every finished hypothesis of a graph must hold.
 
+``coverage`` turns either beam search into coverage-penalised beam search (CoverageBeam; on the device csrc/coverage.hip, the rule in
+csrc/coverage_kernels.h): every hypothesis accumulates the alignment weights of its steps over the graph nodes, and the selection
+prefers hypotheses that have looked at all of them.
+
 ``sample_device`` decodes by sampling instead (csrc/sample.hip): the same fixed slots, one independent sample per slot with
 temperature / top-k / top-p, and Beam objects filled the same way.
 """
@@ -220,6 +224,58 @@ class ConstrainedBeam(Beam):
         return parents
 
 
+class CoveredHypothesis(Hypothesis):
+    __slots__ = ("cp", "coverage")
+
+    def __init__(self, seq, score, cp, coverage):
+        super().__init__(seq, score)
+        self.cp = cp                    # coverage penalty of the step that produced the last token: sum_i log(min(coverage_i, 1) + 1e-12)
+        self.coverage = coverage        # per graph node the alignment weight accumulated up to that step (0 at padded nodes)
+
+
+class CoverageBeam(Beam):
+    """Coverage-penalised beam search of one sentence (the GNMT coverage penalty, Wu et al. 2016, eq. 14): the rule of
+    csrc/coverage_kernels.h in Python.  Beam with the pool sorted by ``score + beta * cp[parent]`` (stable, descending), cp[parent] the
+    penalty of the parent's coverage with this step's alignment weights added; a hypothesis's score stays the model's log-likelihood,
+    and it records the cp and the coverage it was selected with.  get_k_best ranks by GNMT's s(Y, X)."""
+
+    def __init__(self, beam_size, min_time_step, max_time_step, beta):
+        assert 0 <= beta < float('inf')
+        super().__init__(beam_size, min_time_step, max_time_step)
+        self.beta = float(beta)
+        self.hypotheses = [CoveredHypothesis([STR], 0., 0., [])]
+
+    def advance(self, last_steps, cp, coverage):
+        """last_steps as in Beam.advance; cp[h] / coverage[h]: the penalty and the coverage (a list of floats) of live hypothesis h at
+        this step.  Returns the parents like Beam.advance."""
+        pool = []
+        for parent, steps in enumerate(last_steps):
+            base = self.hypotheses[parent].score
+            for token, ll in steps:
+                score = float('-inf') if token == UNK else base + ll
+                pool.append((parent, token, score, score + self.beta * cp[parent]))
+        pool.sort(key=lambda c: c[3], reverse=True)                     # stable: ties keep (parent, rank) order
+        pool = pool[:self.beam_size - len(self.completed_hypotheses)]
+        alive, parents = [], []
+        for parent, token, score, _ in pool:
+            hyp = CoveredHypothesis(self.hypotheses[parent].seq + [token], score, cp[parent], coverage[parent])
+            if hyp.is_completed():
+                if len(hyp) - 2 >= self.min_time_step:
+                    self.completed_hypotheses.append(hyp)
+            else:
+                alive.append(hyp)
+                parents.append(parent)
+        self.hypotheses = alive
+        self.steps += 1
+        return parents
+
+    def get_k_best(self, k, alpha):
+        if not self.completed_hypotheses:
+            self.completed_hypotheses = self.hypotheses
+        self.completed_hypotheses.sort(key=lambda h: h.score / ((1 + len(h.seq)) ** alpha) + self.beta * h.cp, reverse=True)
+        return self.completed_hypotheses[:k]
+
+
 def constraints_met(seq, constraints):
     """How many distinct strings of ``constraints`` occur in ``seq`` (a list of token strings, e.g. Hypothesis.seq)."""
     have = set(seq)
@@ -245,7 +301,7 @@ def banned_tokens(y, n):
     return [y[i + n - 1] for i in range(t - n + 1) if y[i:i + n - 1] == suffix]
 
 
-def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None):
+def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage=None):
     """Runs all beams to completion.  ``model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, topk)`` ->
     (state, results); ``state`` is opaque here except that every tensor in it has the hypothesis axis at dim 1.  With
     ``no_repeat_ngram`` = n > 0 the call also gets, per hypothesis, the output ids that would repeat an n-gram of its tokens
@@ -254,11 +310,21 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
     settings and then holds that search's result (gather_groups).
     ``constraints`` (one list of token strings per graph, not with groups): lexically constrained search -- every (fresh) beam is
     searched as a ConstrainedBeam and then holds that search's lists, steps and ``met``; the decode call also gets ``want``, per
-    hypothesis the output ids of its graph's constraints, and returns their log-likelihoods after banning."""
+    hypothesis the output ids of its graph's constraints, and returns their log-likelihoods after banning.
+    ``coverage`` = beta (not with groups or constraints): coverage-penalised search -- every (fresh) beam is searched as a
+    CoverageBeam and then holds that search's lists and steps; the decode call also returns the alignment weights, the live hypotheses'
+    coverage is one device tensor gathered with the caches, ops.coverage_step (the kernel of the device search, a hypothesis its own
+    parent) adds and reduces it, and the host reads penalty and coverage in one copy per step."""
     device = memory['probe'].device
     state = None
     result = beams
-    if constraints is not None:
+    cov = None
+    if coverage is not None:
+        assert groups == 1 and diversity == 0.0 and constraints is None, "coverage: no groups, no constraints"
+        beams = [CoverageBeam(b.beam_size, b.min_time_step, b.max_time_step, coverage) for b in beams]
+        live = lambda beam: beam.hypotheses
+        ones = torch.ones(3, dtype=torch.int32, device=device)
+    elif constraints is not None:
         assert groups == 1 and diversity == 0.0 and len(constraints) == len(beams), "constraints: one list per graph, no groups"
         beams = [ConstrainedBeam(b.beam_size, b.min_time_step, b.max_time_step, c) for b, c in zip(beams, constraints)]
         cons_id = constraint_ids(model, memory['local_idx2token'], constraints)
@@ -290,6 +356,14 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
             state, results, lls = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size,
                                                             banned if no_repeat_ngram else None, want=[cons_id[bi] for bi in owners])
             forced = [list(zip(constraints[bi], row)) for bi, row in zip(owners, lls)]
+        elif coverage is not None:
+            state, results, align = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size,
+                                                              banned if no_repeat_ngram else None, want_align=True)
+            pad = memory['graph_padding_mask'].index_select(1, beam_of_hyp).contiguous()
+            prev, cov = torch.zeros_like(align) if cov is None else cov, torch.empty_like(align)
+            cp = torch.empty(len(owners), dtype=torch.float64, device=device)
+            ops.coverage_step(offset, 1, align, pad, None, prev, cov, cp, ones)
+            rows = torch.cat([cp.unsqueeze(1), cov.masked_fill(pad.t(), 0.).double()], 1).tolist()       # the step's one extra read
         elif no_repeat_ngram:
             state, results = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size, banned)
         else:
@@ -300,7 +374,12 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
             if beam.completed():
                 continue
             n = len(live(beam))
-            parents = beam.advance(results[pos:pos + n]) if forced is None else beam.advance(results[pos:pos + n], forced[pos:pos + n])
+            if coverage is not None:
+                parents = beam.advance(results[pos:pos + n], [r[0] for r in rows[pos:pos + n]], [r[1:] for r in rows[pos:pos + n]])
+            elif forced is None:
+                parents = beam.advance(results[pos:pos + n])
+            else:
+                parents = beam.advance(results[pos:pos + n], forced[pos:pos + n])
             if not beam.completed():
                 keep.extend(pos + p for p in parents)
             pos += n
@@ -308,9 +387,13 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
             break
         idx = torch.tensor(keep, dtype=torch.int64, device=device)
         state = {k: [c.index_select(1, idx) for c in v] for k, v in state.items()}
+        if coverage is not None:
+            cov = cov.index_select(0, idx)
     if result is not beams:
         for beam, run in zip(result, beams):
-            if constraints is not None:
+            if coverage is not None:
+                beam.hypotheses, beam.completed_hypotheses, beam.steps = run.hypotheses, run.completed_hypotheses, run.steps
+            elif constraints is not None:
                 beam.hypotheses, beam.completed_hypotheses, beam.steps, beam.met = run.hypotheses, run.completed_hypotheses, run.steps, run.met
             else:
                 gather_groups(beam, run.groups)
@@ -334,7 +417,8 @@ def _arena(dtype, cuts, dev):
     return views, lambda: {cut[0]: part.tolist() for cut, part in zip(cuts, torch.split(flat.cpu(), sizes))}
 
 
-def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, layout, step, fill, no_repeat_ngram=0, taken=None):
+def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, layout, step, fill, no_repeat_ngram=0, taken=None,
+                 want_align=False, extra_reads=0):
     """The fixed-slot decode loop (the contract of csrc/slot_kernels.h) behind ``who``, a public function: B graphs x k slots, N = B*k,
     slot s belongs to graph s // k, the graph memory gathered per slot once, every slot decoded every step (a dead slot on the
     padding input), the input of step t + 1 written by step t's kernels into the other of two buffers.  The loop reads the device's
@@ -350,7 +434,9 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
       fill(beams, k, token_string=, **tables) -> the Beam objects from its tables as flat lists; token_string(b, id) -> the string;
       taken(d, t) -> (parent [N] int32 or None, token [N] int32): what every slot took at step t (a negative entry: a dead slot), for
         ``no_repeat_ngram`` = n > 0, the rule of csrc/ngram_kernels.h: two int32 [N, max_t] history buffers alternate by step parity and
-        ops.ngram_block bans, in ll, the columns that would repeat an n-gram, at every step t >= 1 before step().  n = 0: nothing of it."""
+        ops.ngram_block bans, in ll, the columns that would repeat an n-gram, at every step t >= 1 before step().  n = 0: nothing of it.
+      want_align: the decoder also returns the slots' alignment weights [N, n] fp32, which step() finds as d.align;
+      extra_reads: host reads fill() makes beyond the two arenas, counted in stats['host_reads']."""
     B = len(beams)
     if not B:
         return beams
@@ -386,7 +472,10 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     hist = [torch.zeros((N, max_t), dtype=torch.int32, device=dev) for _ in range(2)] if no_repeat_ngram else None
     for t in range(max_t):
         cur, nxt = t % 2, (t + 1) % 2
-        ll = model.decode_slots((tok[cur], chars[cur]), caches[cur % copies], mem, t)
+        if want_align:
+            ll, d.align = model.decode_slots((tok[cur], chars[cur]), caches[cur % copies], mem, t, want_align=True)
+        else:
+            ll = model.decode_slots((tok[cur], chars[cur]), caches[cur % copies], mem, t)
         if no_repeat_ngram and t:
             parent, token = taken(d, t - 1)
             ops.ngram_block(t, k, no_repeat_ngram, ll, parent, token, hist[nxt], hist[cur], ints['active'])
@@ -398,7 +487,7 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
                 break
     host = dict(read_ints(), **read_dbls())
     del host['active']
-    reads += 2
+    reads += 2 + extra_reads
     if stats is not None:
         stats.update(steps=n_steps, host_reads=reads)
     pv = model.vocabs['predictable_token']
@@ -406,7 +495,7 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
 
 
 def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0, groups=1, diversity=0.0, grouped=None,
-                       constraints=None, constrained=None):
+                       constraints=None, constrained=None, coverage=None, covered=None):
     """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
     decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
     steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
@@ -421,11 +510,20 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat
     csrc/constrain_kernels.h, ConstrainedBeam on the host) -- the plain tables plus the slots' masks ``met`` and the constraint ids, a
     step's advance being gtos_constrain_advance between the plain top-k and the plain reorder; a beam then also carries ``met``, the
     masks of its live hypotheses.  ``constrained`` = True takes that route even without constraints (it must give the plain search's
-    beams)."""
+    beams).
+    ``coverage`` = beta (not with groups or constraints): coverage-penalised search (the rule of csrc/coverage_kernels.h, CoverageBeam
+    on the host) -- per step gtos_coverage_step before the plain top-k and gtos_coverage_advance as the advance, the plain reorder; a
+    beam's hypotheses are then CoveredHypothesis objects.  ``covered`` = True takes that route even without a penalty (beta = 0: it
+    must give the plain search's beams, with the coverage reported)."""
     if grouped is None:
         grouped = groups != 1 or diversity != 0.0
     if constrained is None:
         constrained = constraints is not None
+    if covered is None:
+        covered = coverage is not None
+    if covered:
+        assert not grouped and not constrained, "coverage does not combine with groups or constraints"
+        return _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, 0.0 if coverage is None else float(coverage))
     if constrained:
         assert not grouped, "constraints do not combine with groups"
         return _constrained_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, constraints)
@@ -513,6 +611,57 @@ def _constrained_search_device(model, memory, beams, sync_every, stats, no_repea
     for beam in beams:
         if getattr(beam, 'met', None) is None:               # no step ran (max_time_step <= 0)
             beam.met = [0]
+    return beams
+
+
+def _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, beta):
+    """The coverage route of beam_search_device.  Per step: the decoder (which also hands out its alignment weights),
+    gtos_ngram_block if asked, gtos_coverage_step (coverage and penalty of every slot, two [N, n] buffers alternating by step parity as
+    the n-gram histories do), gtos_beam_topk, gtos_coverage_advance, gtos_beam_reorder.  The fp64 arena also holds slot_cp / comp_cp;
+    the fp32 tables slot_cov [N, n] / comp_cov [B, k, n] cost one more host read at the end."""
+    assert 0 <= beta < float('inf'), "coverage: a finite weight >= 0"
+
+    tables = types.SimpleNamespace()                         # the fp32 tables and the step's scratch, which no arena holds
+
+    def layout(d):
+        c, mask = tables, memory['graph_padding_mask']
+        n, dev = mask.shape[0], mask.device
+        c.pad = mask.repeat_interleave(d.k, dim=1).contiguous()              # [n, N]: slot s reads graph s // k
+        c.cov = [torch.zeros((d.N, n), dtype=torch.float32, device=dev) for _ in range(2)]
+        c.cp = torch.zeros(d.N, dtype=torch.float64, device=dev)
+        c.slot_cov = torch.zeros((d.N, n), dtype=torch.float32, device=dev)
+        c.comp_cov = torch.zeros((d.B, d.k, n), dtype=torch.float32, device=dev)
+        return ([('state', (d.B, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
+                 ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0)],
+                [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0), ('slot_cp', (d.N,), 0), ('comp_cp', (d.B, d.k), 0)])
+
+    def step(d, t, ll, cur, nxt, tok_out, char_out):
+        a, tab, c = d.arr, d.tab, tables
+        ops.coverage_step(t, d.k, d.align, c.pad, a['bp_parent'][t - 1] if t else None, c.cov[(t + 1) % 2], c.cov[t % 2], c.cp, a['active'])
+        topv, topi = ops.beam_topk(ll, d.k)
+        ops.coverage_advance(t, d.k, beta, d.V, d.tot, d.min_t, d.max_t, topv, topi, tab['flag_shared'], tab['flag_local'], a['slot_score'],
+                             a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'], c.cp,
+                             c.cov[t % 2], a['slot_cp'], a['comp_cp'], c.comp_cov, c.slot_cov, a['active'])
+        ops.beam_reorder(cur, nxt, t, d.k, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
+                         tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+
+    def fill(beams_, k, slot_cp, comp_cp, state, **plain):
+        c, N = tables, len(beams_) * k
+        keep = (~c.pad.t()).to(torch.float32)                # [N, n]: 0 at the padded nodes of the slot's graph
+        rows = torch.cat([c.slot_cov * keep, c.comp_cov.view(N, -1) * keep]).tolist()           # a completion row b*k + j is of graph b too
+        fill_beams(beams_, k, state=state, **plain)
+        for b, beam in enumerate(beams_):
+            if not state[4 * b]:
+                continue
+            beam.completed_hypotheses = [CoveredHypothesis(h.seq, h.score, comp_cp[b * k + j], rows[N + b * k + j])
+                                         for j, h in enumerate(beam.completed_hypotheses)]
+            beam.hypotheses = [CoveredHypothesis(h.seq, h.score, slot_cp[b * k + j], rows[b * k + j]) for j, h in enumerate(beam.hypotheses)]
+        return beams_
+    _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill, no_repeat_ngram,
+                 lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]), want_align=True, extra_reads=1)
+    for beam in beams:
+        if beam.steps == 0:                                  # no step ran (max_time_step <= 0)
+            beam.hypotheses = [CoveredHypothesis([STR], 0., 0., [])]
     return beams
 
 

@@ -546,6 +546,33 @@ int gtos_constrain_advance(int B, int k, int Cw, int t, int V, int tot, int min_
                            int* bp_parent, int* bp_token, int* comp_step, int* comp_parent, double* comp_score, int* met,
                            int* active, void* stream);
 
+/* ---- Coverage-penalised beam search on the device (ABI 29; csrc/coverage.hip, the rule in csrc/coverage_kernels.h), driven by
+ * gtos_amd.search.beam_search_device(coverage=) and, for _step, by the host search and Generator.coverage as well: the GNMT coverage
+ * penalty (Wu et al., "Google's Neural Machine Translation System", eq. 14) over the copy mechanism's alignment weights
+ * (generator/decoder.py:32-34).  The rule has no counterpart in generator/search.py.  The top-k pass is gtos_beam_topk(ll, k), the
+ * reorder gtos_beam_reorder.
+ * _step (one workgroup per slot; per step after the decoder and gtos_ngram_block, before the top-k): align fp32 [N, n] the alignment
+ *   weights of step t, pad uint8 [n, N] (1: padding node), parent int32 [N] what every slot took as parent at step t - 1 (row t - 1 of
+ *   bp_parent; NULL: a slot is its own parent).  cov_cur[s, :] = cov_prev[parent[s], :] + align[s, :] (fp32 [N, n] each, one add; the
+ *   caller alternates the two buffers by step parity and starts from zeros) and cp[s] (fp64 [N]) = the sum over the nodes that are
+ *   not padding of (double) logf(fminf(cov_cur, 1) + 1e-12f), in an order that depends on n alone.  A slot with parent < 0 (or >= N)
+ *   is dead: a zero row and cp = 0.  active int32 [3] as in csrc/slot_kernels.h, read only: a step that does not run writes nothing.
+ *   SHAPES (-10 outside): n >= 1, t >= 0, N % k == 0, cov_prev != cov_cur; -23 for a null pointer (parent may be null).
+ * _advance (one workgroup per graph, step t < max_time_step): gtos_beam_advance with the pool ranked by
+ *   score + beta * cp[parent slot] (fp64; beta_bits: the bit pattern of the fp64 beta, finite and >= 0; beta = 0 gives
+ *   gtos_beam_advance's tables); every stored score stays the log-likelihood.  Beside the tables of gtos_beam_advance it writes
+ *   slot_cp fp64 [N] / slot_cov fp32 [N, n] (per surviving slot, the penalty and the cov_cur row of its parent) and comp_cp fp64
+ *   [B, k] / comp_cov fp32 [B, k, n] (the same per completion, in append order).
+ *   SHAPES (-10 outside): 1 <= k <= 32, 0 <= t < max_time_step, 1 <= V <= tot, n >= 1; -23 for a null pointer (flag_local may be
+ *   null when tot == V). */
+int gtos_coverage_step(int N, int k, int t, int n, const float* align, const uint8_t* pad, const int* parent,
+                       const float* cov_prev, float* cov_cur, double* cp, const int* active, void* stream);
+int gtos_coverage_advance(int B, int k, int t, int V, int tot, int min_time_step, int max_time_step, uint64_t beta_bits, int n,
+                          const float* topv, const int* topi, const uint8_t* flag_shared, const uint8_t* flag_local,
+                          double* slot_score, int* beam_state, int* bp_parent, int* bp_token, int* comp_step, int* comp_parent,
+                          double* comp_score, const double* cp, const float* cov_cur, double* slot_cp, double* comp_cp,
+                          float* comp_cov, float* slot_cov, int* active, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
