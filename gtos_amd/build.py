@@ -51,13 +51,13 @@ def build_host(force=False, verbose=True):
 def build(force=False, verbose=True):
     build_host(force, verbose)
     own_hdr = {"pathtrie_dev.hip": "trie_kernels.h", "relbatch_dev.hip": "relbatch_kernels.h",
-               "relindex_dev.hip": "relindex_kernels.h", "beam.hip": "beam_kernels.h slot_kernels.h slot_device.h reorder_device.h",
+               "relindex_dev.hip": "relindex_kernels.h", "beam.hip": "beam_kernels.h beam_device.h slot_kernels.h slot_device.h reorder_device.h",
                "sample.hip": "sample_kernels.h slot_kernels.h slot_device.h", "copy_ls.hip": "copy_ls_kernels.h",
                "copy_nll.hip": "copy_row.h", "rel_attn.hip": "common.h attn_tile.h", "attn_tile.hip": "common.h attn_tile.h",
                "copy_eval.hip": "copy_eval_kernels.h", "ngram.hip": "common.h ngram_kernels.h slot_kernels.h",
-               "diverse.hip": "diverse_kernels.h beam_kernels.h slot_kernels.h slot_device.h reorder_device.h",
-               "constrain.hip": "constrain_kernels.h beam_kernels.h slot_kernels.h slot_device.h common.h",
-               "coverage.hip": "coverage_kernels.h beam_kernels.h slot_kernels.h slot_device.h common.h"}     # the others include common.h
+               "diverse.hip": "diverse_kernels.h beam_kernels.h beam_device.h slot_kernels.h slot_device.h reorder_device.h",
+               "constrain.hip": "constrain_kernels.h beam_kernels.h beam_device.h slot_kernels.h slot_device.h common.h",
+               "coverage.hip": "coverage_kernels.h beam_kernels.h beam_device.h slot_kernels.h slot_device.h common.h"}     # the others include common.h
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -2,6 +2,7 @@
 // rule in csrc/beam_kernels.h, shared with the host check), and the reorder of the self-attention caches by parent slot together with
 // the next step's input token ids and character rows.  Nothing here synchronises with the host; the per-beam state, back-pointers and
 // completions stay on the device until the search ends.
+#include "beam_device.h"
 #include "beam_kernels.h"
 #include "reorder_device.h"
 #include "slot_device.h"
@@ -26,25 +27,9 @@ __global__ __launch_bounds__(NT) void beam_topk_kernel(int tot, int k, const flo
     }
 }
 
-struct AdvanceArgs {
-    int B, k, t, V, tot, min_t, max_t;
-    const float* topv;
-    const int* topi;
-    const uint8_t* flag_shared;
-    const uint8_t* flag_local;
-    double* slot_score;
-    int* state;
-    int* bp_parent;
-    int* bp_token;
-    int* comp_step;
-    int* comp_parent;
-    double* comp_score;
-    int* active;
-};
-
 // One workgroup per beam.  The active[3] rotation of csrc/slot_kernels.h; the flag: did any not-done beam have a live slot when this
 // iteration started?
-__global__ __launch_bounds__(NT) void beam_advance_kernel(AdvanceArgs a) {
+__global__ __launch_bounds__(NT) void beam_advance_kernel(BeamTables a) {
     __shared__ double ps[MAX_K * MAX_K];
     __shared__ int pt[MAX_K * MAX_K];
     __shared__ uint8_t pf[MAX_K * MAX_K];
@@ -53,8 +38,10 @@ __global__ __launch_bounds__(NT) void beam_advance_kernel(AdvanceArgs a) {
     if (b == 0 && threadIdx.x == 0) a.active[active_clear(t)] = 0;
     const int* st = a.state + (int64_t)b * BS_WORDS;
     if (!a.active[active_read(t)] || st[BS_DONE]) return;
-    const int P = st[BS_NLIVE] * a.k;
-    const int m = cut_size(P, a.k, st[BS_NCOMP]);
+    const int nlive = st[BS_NLIVE], ncomp = st[BS_NCOMP];
+    if (!words_in_range(nlive, ncomp, a.k)) return;
+    const int P = nlive * a.k;
+    const int m = cut_size(P, a.k, ncomp);
     for (int p = threadIdx.x; p < P; p += NT)
         pool_entry(b, a.k, p, a.topv, a.topi, a.slot_score, a.flag_shared, a.flag_local, a.V, a.tot, ps + p, pt + p, pf + p);
     __syncthreads();
@@ -90,15 +77,10 @@ extern "C" int gtos_beam_advance(int B, int k, int t, int V, int tot, int min_ti
                                  int* beam_state, int* bp_parent, int* bp_token, int* comp_step, int* comp_parent,
                                  double* comp_score, int* active, void* stream) {
     if (B <= 0) return 0;
-    if (k < 1 || k > MAX_K || t < 0 || t >= max_time_step || V < 1 || tot < V) return -10;
-    if (!topv || !topi || !flag_shared || (tot > V && !flag_local) || !slot_score || !beam_state || !bp_parent || !bp_token ||
-        !comp_step || !comp_parent || !comp_score || !active)
-        return -23;
-    AdvanceArgs a{};
-    a.B = B; a.k = k; a.t = t; a.V = V; a.tot = tot; a.min_t = min_time_step; a.max_t = max_time_step;
-    a.topv = topv; a.topi = topi; a.flag_shared = flag_shared; a.flag_local = flag_local; a.slot_score = slot_score;
-    a.state = beam_state; a.bp_parent = bp_parent; a.bp_token = bp_token; a.comp_step = comp_step; a.comp_parent = comp_parent;
-    a.comp_score = comp_score; a.active = active;
+    const BeamTables a{B, k, t, V, tot, min_time_step, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state,
+                       bp_parent, bp_token, comp_step, comp_parent, comp_score, active};
+    if (!sizes_ok(a)) return -10;
+    if (!tables_ok(a)) return -23;
     hipLaunchKernelGGL(beam_advance_kernel, dim3((unsigned)B), dim3(NT), 0, static_cast<hipStream_t>(stream), a);
     GTOS_CHECK_LAUNCH();
     return 0;

@@ -2,7 +2,7 @@
 // Dynamic Beam Allocation", single-token constraints), written so that the SAME code compiles for the host:
 // tests/test_constrained_beam.py builds it with g++ and compares a serial advance (advance_serial) with
 // gtos_amd.search.ConstrainedBeam.advance on random pools.  It is the rule of csrc/beam_kernels.h with three additions; cand_score,
-// before, cut_size and the state words are that header's, and a graph without constraints gets exactly that header's tables.
+// before, cut_size, place_cut and the state words are that header's, and a graph without constraints gets exactly that header's tables.
 //
 // Constraints: cons int32 [B, Cw], row b the output ids graph b must produce, c_b of them (at most MAX_CONS), then -1.  An id outside
 // [0, tot) ends the row like -1 does.  The ids of a row are distinct and of the plain string class (the caller's contract;
@@ -19,7 +19,7 @@
 //    A present entry has mask' = met[slot] | (bit i for the i with id == cons[b][i]) and bank = popcount(mask').
 // 3. Order.  Absent entries are never placed.  Within a bank, q is the entry's rank under before(score, p) (stable, descending).  The
 //    final order is ascending q, then descending bank: the best of every bank from the fullest bank down, then the second best of
-//    every bank, and so on.  The cut is m = min(#present, k - #completed); placement is gtos_beam::place's with parent slot
+//    every bank, and so on.  The cut is m = min(#present, k - #completed); placement is gtos_beam::place_cut's with parent slot
 //    b*k + p / W, and mask' of every survivor goes to the new met row at the survivor's new slot (0 at the beam's other slots).
 //    Scores written are model scores.
 //
@@ -108,42 +108,24 @@ GTOS_BEAM_HD int final_position(const int* q, const signed char* bank, int P, in
     return r;
 }
 
-// gtos_beam::place for a pool of W entries per slot that also writes the beam's slots of the new met row: order[r] = pool position of
-// the r-th entry of the final order, m entries.  Returns true when the beam stays not-done with live slots.
+// place_cut's hook of this rule: mask' of every survivor goes to the new met row at its new slot
+struct MetHook {
+    const int* pool_mask;
+    int* met_next;
+    GTOS_BEAM_HD void live(int p, int, int dst) const { met_next[dst] = pool_mask[p]; }
+    GTOS_BEAM_HD void done(int, int, int) const {}
+};
+
+// gtos_beam::place_cut for a pool of W entries per slot that also writes the beam's slots of the new met row (0 where no survivor
+// lands): order[r] = pool position of the r-th entry of the final order, m entries.  Returns true when the beam stays not-done with
+// live slots.
 GTOS_BEAM_HD bool place(int b, int k, int W, int min_time_step, int max_time_step, const int* order, int m, const double* pool_score,
                         const int* pool_tok, const uint8_t* pool_flag, const int* pool_mask, int t, int* state, int* bp_parent_t,
                         int* bp_token_t, double* slot_score, int* comp_step, int* comp_parent, double* comp_score, int* met_next) {
-    int* st = state + (int64_t)b * BS_WORDS;
-    const int steps = st[BS_STEPS];
-    int ncomp = st[BS_NCOMP], nlive = 0;
-    for (int j = 0; j < k; ++j) {
-        bp_parent_t[b * k + j] = -1;
-        bp_token_t[b * k + j] = -1;
-        met_next[b * k + j] = 0;
-    }
-    for (int r = 0; r < m; ++r) {
-        const int p = order[r];
-        const int parent = b * k + p / W;
-        if (pool_flag[p] == TOK_END) {
-            if (steps >= min_time_step) {
-                comp_step[b * k + ncomp] = t;
-                comp_parent[b * k + ncomp] = parent;
-                comp_score[b * k + ncomp] = pool_score[p];
-                ++ncomp;
-            }
-        } else {
-            bp_parent_t[b * k + nlive] = parent;
-            bp_token_t[b * k + nlive] = pool_tok[p];
-            slot_score[b * k + nlive] = pool_score[p];
-            met_next[b * k + nlive] = pool_mask[p];
-            ++nlive;
-        }
-    }
-    st[BS_STEPS] = steps + 1;
-    st[BS_NCOMP] = ncomp;
-    st[BS_NLIVE] = nlive;
-    st[BS_DONE] = ncomp >= k || steps + 1 >= max_time_step;
-    return !st[BS_DONE] && nlive > 0;
+    for (int j = 0; j < k; ++j) met_next[b * k + j] = 0;
+    return place_cut(b * k, k, W, min_time_step, max_time_step, order, m, pool_score, pool_tok, pool_flag, t,
+                     state + (int64_t)b * BS_WORDS, bp_parent_t, bp_token_t, slot_score, comp_step, comp_parent, comp_score,
+                     MetHook{pool_mask, met_next});
 }
 
 // The whole advance of one beam by one thread (the host check; the kernel parallelises the pool and the two rankings).  pool_* are

@@ -2,6 +2,7 @@
 // Generator.coverage launch the first kernel too): the per-slot coverage of the graph nodes with its penalty, and the beams' advance
 // ranked by score + beta * penalty (rule in csrc/coverage_kernels.h, shared with the host check).  The top-k pass is gtos_beam_topk,
 // the reorder gtos_beam_reorder; nothing here synchronises with the host.
+#include "beam_device.h"
 #include "common.h"
 #include "coverage_kernels.h"
 #include "slot_device.h"
@@ -57,26 +58,15 @@ __global__ __launch_bounds__(NT) void coverage_step_kernel(StepArgs a) {
 }
 
 struct AdvanceArgs {
-    int B, k, t, V, tot, min_t, max_t, n;
+    BeamTables tb;
+    int n;
     double beta;
-    const float* topv;
-    const int* topi;
-    const uint8_t* flag_shared;
-    const uint8_t* flag_local;
-    double* slot_score;
-    int* state;
-    int* bp_parent;
-    int* bp_token;
-    int* comp_step;
-    int* comp_parent;
-    double* comp_score;
     const double* cp;
     const float* cov_cur;
     double* slot_cp;
     double* comp_cp;
     float* comp_cov;
     float* slot_cov;
-    int* active;
 };
 
 // One workgroup per beam, as beam_advance_kernel: the pool and its keys filled and ranked by all threads, the cut placed by one, which
@@ -91,17 +81,18 @@ __global__ __launch_bounds__(NT) void coverage_advance_kernel(AdvanceArgs a) {
     __shared__ int row_src[2 * MAX_K];       // slot whose cov_cur row is copied ...
     __shared__ int row_dst[2 * MAX_K];       // ... to row r of comp_cov (r < N) or row r - N of slot_cov
     __shared__ int n_rows;
-    const int b = blockIdx.x, t = a.t, k = a.k;
-    if (b == 0 && threadIdx.x == 0) a.active[active_clear(t)] = 0;
-    const int* st = a.state + (int64_t)b * BS_WORDS;
-    if (!a.active[active_read(t)] || st[BS_DONE]) return;
+    const BeamTables& tb = a.tb;
+    const int b = blockIdx.x, t = tb.t, k = tb.k;
+    if (b == 0 && threadIdx.x == 0) tb.active[active_clear(t)] = 0;
+    const int* st = tb.state + (int64_t)b * BS_WORDS;
+    if (!tb.active[active_read(t)] || st[BS_DONE]) return;
     const int nlive0 = st[BS_NLIVE], ncomp0 = st[BS_NCOMP];
-    if (nlive0 < 0 || nlive0 > k || ncomp0 < 0 || ncomp0 >= k) return;      // (words outside a beam's range: left alone)
+    if (!words_in_range(nlive0, ncomp0, k)) return;
     const int P = nlive0 * k;
     const int m = cut_size(P, k, ncomp0);
-    const int64_t N = (int64_t)a.B * k;
+    const int64_t N = (int64_t)tb.B * k;
     for (int p = threadIdx.x; p < P; p += NT) {
-        pool_entry(b, k, p, a.topv, a.topi, a.slot_score, a.flag_shared, a.flag_local, a.V, a.tot, ps + p, pt + p, pf + p);
+        pool_entry(b, k, p, tb.topv, tb.topi, tb.slot_score, tb.flag_shared, tb.flag_local, tb.V, tb.tot, ps + p, pt + p, pf + p);
         pk[p] = key_of(ps[p], a.beta, a.cp[b * k + p / k]);
     }
     __syncthreads();
@@ -111,14 +102,14 @@ __global__ __launch_bounds__(NT) void coverage_advance_kernel(AdvanceArgs a) {
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        int* bp_parent_t = a.bp_parent + t * N;
-        if (place(b, k, a.min_t, a.max_t, order, m, ps, pt, pf, t, a.state, bp_parent_t, a.bp_token + t * N, a.slot_score,
-                  a.comp_step, a.comp_parent, a.comp_score, a.cp, a.slot_cp, a.comp_cp))
-            atomicOr(a.active + active_set(t), 1);
-        const int* st1 = a.state + (int64_t)b * BS_WORDS;
+        int* bp_parent_t = tb.bp_parent + t * N;
+        if (place(b, k, tb.min_t, tb.max_t, order, m, ps, pt, pf, t, tb.state, bp_parent_t, tb.bp_token + t * N, tb.slot_score,
+                  tb.comp_step, tb.comp_parent, tb.comp_score, a.cp, a.slot_cp, a.comp_cp))
+            atomicOr(tb.active + active_set(t), 1);
+        const int* st1 = tb.state + (int64_t)b * BS_WORDS;
         int nr = 0;
         for (int j = ncomp0; j < st1[BS_NCOMP] && j < k; ++j) {
-            row_src[nr] = a.comp_parent[b * k + j];
+            row_src[nr] = tb.comp_parent[b * k + j];
             row_dst[nr++] = b * k + j;
         }
         for (int j = 0; j < st1[BS_NLIVE] && j < k; ++j) {
@@ -162,17 +153,12 @@ extern "C" int gtos_coverage_advance(int B, int k, int t, int V, int tot, int mi
     double beta;
     static_assert(sizeof beta == sizeof beta_bits, "the penalty weight travels as the bit pattern of an fp64");
     memcpy(&beta, &beta_bits, sizeof beta);
-    if (k < 1 || k > MAX_K || t < 0 || t >= max_time_step || V < 1 || tot < V || n < 1 || !beta_ok(beta)) return -10;
+    const AdvanceArgs a{{B, k, t, V, tot, min_time_step, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state,
+                         bp_parent, bp_token, comp_step, comp_parent, comp_score, active},
+                        n, beta, cp, cov_cur, slot_cp, comp_cp, comp_cov, slot_cov};
+    if (!sizes_ok(a.tb) || n < 1 || !beta_ok(beta)) return -10;
     if ((int64_t)B * k * 2 > INT_MAX) return -10;
-    if (!topv || !topi || !flag_shared || (tot > V && !flag_local) || !slot_score || !beam_state || !bp_parent || !bp_token ||
-        !comp_step || !comp_parent || !comp_score || !cp || !cov_cur || !slot_cp || !comp_cp || !comp_cov || !slot_cov || !active)
-        return -23;
-    AdvanceArgs a{};
-    a.B = B; a.k = k; a.t = t; a.V = V; a.tot = tot; a.min_t = min_time_step; a.max_t = max_time_step; a.n = n; a.beta = beta;
-    a.topv = topv; a.topi = topi; a.flag_shared = flag_shared; a.flag_local = flag_local; a.slot_score = slot_score;
-    a.state = beam_state; a.bp_parent = bp_parent; a.bp_token = bp_token; a.comp_step = comp_step; a.comp_parent = comp_parent;
-    a.comp_score = comp_score; a.cp = cp; a.cov_cur = cov_cur; a.slot_cp = slot_cp; a.comp_cp = comp_cp; a.comp_cov = comp_cov;
-    a.slot_cov = slot_cov; a.active = active;
+    if (!tables_ok(a.tb) || !cp || !cov_cur || !slot_cp || !comp_cp || !comp_cov || !slot_cov) return -23;
     hipLaunchKernelGGL(coverage_advance_kernel, dim3((unsigned)B), dim3(NT), 0, static_cast<hipStream_t>(stream), a);
     GTOS_CHECK_LAUNCH();
     return 0;

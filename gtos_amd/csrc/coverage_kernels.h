@@ -1,7 +1,7 @@
 // Selection rule of the coverage-penalised beam search (csrc/coverage.hip; the GNMT coverage penalty, Wu et al. 2016, eq. 14), written
 // so that the SAME code compiles for the host: tests/test_coverage_beam.py builds it with g++ and compares a serial advance
 // (advance_serial) with gtos_amd.search.CoverageBeam.advance on random pools.  It is the rule of csrc/beam_kernels.h with another
-// ranking key; cand_score, before, rank_of, pool_entry, cut_size and the state words are that header's.
+// ranking key; cand_score, before, rank_of, pool_entry, cut_size, place_cut and the state words are that header's.
 //
 // Slots as in csrc/slot_kernels.h.  n: the node rows of the graph memory; pad [n, N] (uint8, 1: node i of slot s's graph is padding);
 // a_t [N, n] fp32: the alignment weights of step t (TokenGenerator.alignment_layer, the row the copy mechanism reads), known before
@@ -37,25 +37,24 @@ GTOS_BEAM_HD float cp_term(float cov) { return logf(fminf(cov, 1.0f) + 1e-12f); 
 // Python's `score + beta * cp`
 GTOS_BEAM_HD double key_of(double score, double beta, double cp) { return score + beta * cp; }
 
+// place_cut's hook of this rule: every survivor records this step's penalty of its parent
+struct PenaltyHook {
+    const double* cp;
+    double* slot_cp;
+    double* comp_cp;
+    GTOS_BEAM_HD void live(int, int parent, int dst) const { slot_cp[dst] = cp[parent]; }
+    GTOS_BEAM_HD void done(int, int parent, int dst) const { comp_cp[dst] = cp[parent]; }
+};
+
 // gtos_beam::place that also records the parent's penalty of every survivor: slot_cp [N] next to slot_score, comp_cp [B, k] next to
 // comp_score.  cp [N]: this step's penalty of every slot (read at the parents only).
 GTOS_BEAM_HD bool place(int b, int k, int min_time_step, int max_time_step, const int* order, int m, const double* pool_score,
                         const int* pool_tok, const uint8_t* pool_flag, int t, int* state, int* bp_parent_t, int* bp_token_t,
                         double* slot_score, int* comp_step, int* comp_parent, double* comp_score, const double* cp, double* slot_cp,
                         double* comp_cp) {
-    int ncomp = state[(int64_t)b * BS_WORDS + BS_NCOMP], nlive = 0;
-    const int steps = state[(int64_t)b * BS_WORDS + BS_STEPS];
-    for (int r = 0; r < m; ++r) {
-        const int p = order[r];
-        const double c = cp[b * k + p / k];
-        if (pool_flag[p] == TOK_END) {
-            if (steps >= min_time_step) comp_cp[b * k + ncomp++] = c;
-        } else {
-            slot_cp[b * k + nlive++] = c;
-        }
-    }
-    return gtos_beam::place(b, k, min_time_step, max_time_step, order, m, pool_score, pool_tok, pool_flag, t, state, bp_parent_t,
-                            bp_token_t, slot_score, comp_step, comp_parent, comp_score);
+    return place_cut(b * k, k, k, min_time_step, max_time_step, order, m, pool_score, pool_tok, pool_flag, t,
+                     state + (int64_t)b * BS_WORDS, bp_parent_t, bp_token_t, slot_score, comp_step, comp_parent, comp_score,
+                     PenaltyHook{cp, slot_cp, comp_cp});
 }
 
 // The whole advance of one beam by one thread (the host check; the kernel parallelises the pool and the ranks).  pool_* are scratch

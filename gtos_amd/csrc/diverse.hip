@@ -1,6 +1,7 @@
 // Diverse (group) beam search on the device (gtos_amd.search.beam_search_device with groups / diversity): the advance of every
 // graph's groups (selection rule in csrc/diverse_kernels.h, shared with the host check) and the reorder with per-group liveness
 // (csrc/reorder_device.h, the kernel of gtos_beam_reorder).  The top-k pass is gtos_beam_topk; nothing here synchronises with the host.
+#include "beam_device.h"
 #include "diverse_kernels.h"
 #include "reorder_device.h"
 #include "slot_device.h"
@@ -12,20 +13,9 @@ using namespace gtos_diverse;
 namespace {
 
 struct DiverseArgs {
-    int B, k, G, t, V, tot, min_t, max_t;
+    BeamTables tb;                      // state: one row per group
+    int G;
     double lambda;
-    const float* topv;
-    const int* topi;
-    const uint8_t* flag_shared;
-    const uint8_t* flag_local;
-    double* slot_score;
-    int* state;
-    int* bp_parent;
-    int* bp_token;
-    int* comp_step;
-    int* comp_parent;
-    double* comp_score;
-    int* active;
 };
 
 // One workgroup per graph, its groups one after the other: the pool is filled (the count over the chosen list a linear scan of
@@ -40,22 +30,23 @@ __global__ __launch_bounds__(NT) void diverse_advance_kernel(DiverseArgs a) {
     __shared__ int order[MAX_K];
     __shared__ int chosen[MAX_K];
     __shared__ int n_chosen;
-    const int b = blockIdx.x, t = a.t, g = a.k / a.G;
-    if (b == 0 && threadIdx.x == 0) a.active[active_clear(t)] = 0;
-    if (!a.active[active_read(t)]) return;
+    const BeamTables& tb = a.tb;
+    const int b = blockIdx.x, t = tb.t, k = tb.k, g = k / a.G;
+    if (b == 0 && threadIdx.x == 0) tb.active[active_clear(t)] = 0;
+    if (!tb.active[active_read(t)]) return;
     if (threadIdx.x == 0) n_chosen = 0;
     __syncthreads();
     bool go = false;                     // thread 0's
     for (int j = 0; j < a.G; ++j) {
         const int q = b * a.G + j;
-        const int* st = a.state + (int64_t)q * BS_WORDS;
+        const int* st = tb.state + (int64_t)q * BS_WORDS;
         // the group's words are written by thread 0 only, behind the two barriers below: every thread reads the same values
         const int nlive = st[BS_NLIVE], ncomp = st[BS_NCOMP];
-        if (st[BS_DONE] || nlive < 0 || nlive > g || ncomp < 0 || ncomp >= g) continue;      // (words outside a group's range: left alone)
-        const int P = nlive * a.k, nc = n_chosen;
+        if (st[BS_DONE] || !words_in_range(nlive, ncomp, g)) continue;
+        const int P = nlive * k, nc = n_chosen;
         const int m = cut_size(P, g, ncomp);
         for (int p = threadIdx.x; p < P; p += NT)
-            pool_entry(b, q, g, a.k, p, a.topv, a.topi, a.slot_score, a.flag_shared, a.flag_local, a.V, a.tot, a.lambda, chosen, nc,
+            pool_entry(b, q, g, k, p, tb.topv, tb.topi, tb.slot_score, tb.flag_shared, tb.flag_local, tb.V, tb.tot, a.lambda, chosen, nc,
                        pm + p, pk + p, pt + p, pf + p);
         __syncthreads();
         for (int p = threadIdx.x; p < P; p += NT) {
@@ -64,15 +55,15 @@ __global__ __launch_bounds__(NT) void diverse_advance_kernel(DiverseArgs a) {
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            const int64_t N = (int64_t)a.B * a.k;
+            const int64_t N = (int64_t)tb.B * k;
             int n = nc;
-            go |= place(q, g, a.k, a.min_t, a.max_t, order, m, pm, pt, pf, t, a.state, a.bp_parent + t * N, a.bp_token + t * N,
-                        a.slot_score, a.comp_step, a.comp_parent, a.comp_score, chosen, &n);
+            go |= place(q, g, k, tb.min_t, tb.max_t, order, m, pm, pt, pf, t, tb.state, tb.bp_parent + t * N, tb.bp_token + t * N,
+                        tb.slot_score, tb.comp_step, tb.comp_parent, tb.comp_score, chosen, &n);
             n_chosen = n;
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0 && go) atomicOr(a.active + active_set(t), 1);
+    if (threadIdx.x == 0 && go) atomicOr(tb.active + active_set(t), 1);
 }
 
 }  // namespace
@@ -85,16 +76,10 @@ extern "C" int gtos_diverse_advance(int B, int k, int groups, uint64_t diversity
     double lambda;
     static_assert(sizeof lambda == sizeof diversity_bits, "the penalty travels as the bit pattern of an fp64");
     memcpy(&lambda, &diversity_bits, sizeof lambda);
-    if (k < 1 || k > MAX_K || groups < 1 || k % groups || !lambda_ok(lambda) || t < 0 || t >= max_time_step || V < 1 || tot < V)
-        return -10;
-    if (!topv || !topi || !flag_shared || (tot > V && !flag_local) || !slot_score || !group_state || !bp_parent || !bp_token ||
-        !comp_step || !comp_parent || !comp_score || !active)
-        return -23;
-    DiverseArgs a{};
-    a.B = B; a.k = k; a.G = groups; a.t = t; a.V = V; a.tot = tot; a.min_t = min_time_step; a.max_t = max_time_step; a.lambda = lambda;
-    a.topv = topv; a.topi = topi; a.flag_shared = flag_shared; a.flag_local = flag_local; a.slot_score = slot_score;
-    a.state = group_state; a.bp_parent = bp_parent; a.bp_token = bp_token; a.comp_step = comp_step; a.comp_parent = comp_parent;
-    a.comp_score = comp_score; a.active = active;
+    const DiverseArgs a{{B, k, t, V, tot, min_time_step, max_time_step, topv, topi, flag_shared, flag_local, slot_score, group_state,
+                         bp_parent, bp_token, comp_step, comp_parent, comp_score, active}, groups, lambda};
+    if (!sizes_ok(a.tb) || groups < 1 || k % groups || !lambda_ok(lambda)) return -10;
+    if (!tables_ok(a.tb)) return -23;
     hipLaunchKernelGGL(diverse_advance_kernel, dim3((unsigned)B), dim3(NT), 0, static_cast<hipStream_t>(stream), a);
     GTOS_CHECK_LAUNCH();
     return 0;

@@ -1,7 +1,7 @@
 // Selection rule of the diverse (group) beam search (csrc/diverse.hip; Vijayakumar et al., "Diverse Beam Search", with the Hamming
 // penalty), written so that the SAME code compiles for the host: tests/test_diverse_beam.py builds it with g++ and compares a serial
 // advance (advance_serial) with gtos_amd.search.GroupBeam.advance on random pools.  It is the rule of csrc/beam_kernels.h applied per
-// group; cand_score, before, rank_of, cut_size and the state words are that header's.
+// group; cand_score, before, rank_of, cut_size, place_cut and the state words are that header's.
 //
 // Slots as in csrc/slot_kernels.h: k per graph, cut into G groups of width g = k / G.  Group j of graph b is "group q = b*G + j": it
 // owns slots q*g .. q*g + g - 1 (= b*k + j*g ..), its own state words state[q] = (steps, #completed, #live, done) and rows q*g .. of the
@@ -14,7 +14,7 @@
 // (G = 1 leaves the tables of beam_kernels.h's advance_serial), and it adds nothing to C.  The pool of group j is the top-k candidates (the whole k, not g) of its live slots in (slot, rank) order, position
 // p = i*k + r.  Entry p has the model score m_p = cand_score(slot score, ll, class) and the selection key
 //     key_p = m_p - lambda * count(C, id_p)            (fp64; count with multiplicity)
-// The pool is sorted by KEY (stable, descending: before()), cut to g - #completed and placed as gtos_beam::place places it; every
+// The pool is sorted by KEY (stable, descending: before()), cut to g - #completed and placed as gtos_beam::place_cut places it; every
 // score written to the tables is the MODEL score, never the key, so a hypothesis's score stays its log-likelihood.  The output ids of
 // the entries that survive are appended to C in placement order; completions are not.
 //
@@ -63,43 +63,25 @@ GTOS_BEAM_HD void pool_entry(int b, int q, int g, int k, int p, const float* top
     *flag = f;
 }
 
-// gtos_beam::place for group q of width g whose pool holds k candidates per slot: order[r] = pool position of the r-th best KEY,
-// m entries.  Writes the group's slots of the back-pointer rows, the survivors' MODEL scores, completions at rows q*g + #completed,
-// the group's state words, and appends the survivors' ids to chosen.  Returns true when the group stays not-done with live slots.
+// place_cut's hook of this rule: the output id of every survivor is appended to chosen (n: its length); completions are not
+struct ChosenHook {
+    const int* pool_tok;
+    int* chosen;
+    int* n;
+    GTOS_BEAM_HD void live(int p, int, int) const { chosen[(*n)++] = pool_tok[p]; }
+    GTOS_BEAM_HD void done(int, int, int) const {}
+};
+
+// gtos_beam::place_cut for group q of width g (done at g completions) whose pool holds k candidates per slot: order[r] = pool position
+// of the r-th best KEY, m entries.  Writes the group's slots of the back-pointer rows, the survivors' MODEL scores, completions at rows
+// q*g + #completed, the group's state words, and appends the survivors' ids to chosen.  Returns true when the group stays not-done with
+// live slots.
 GTOS_BEAM_HD bool place(int q, int g, int k, int min_time_step, int max_time_step, const int* order, int m, const double* pool_model,
                         const int* pool_tok, const uint8_t* pool_flag, int t, int* state, int* bp_parent_t, int* bp_token_t,
                         double* slot_score, int* comp_step, int* comp_parent, double* comp_score, int* chosen, int* n_chosen) {
-    int* st = state + (int64_t)q * BS_WORDS;
-    const int steps = st[BS_STEPS], base = q * g;
-    int ncomp = st[BS_NCOMP], nlive = 0, nc = *n_chosen;
-    for (int i = 0; i < g; ++i) {
-        bp_parent_t[base + i] = -1;
-        bp_token_t[base + i] = -1;
-    }
-    for (int r = 0; r < m; ++r) {
-        const int p = order[r];
-        const int parent = base + p / k;
-        if (pool_flag[p] == TOK_END) {
-            if (steps >= min_time_step) {
-                comp_step[base + ncomp] = t;
-                comp_parent[base + ncomp] = parent;
-                comp_score[base + ncomp] = pool_model[p];
-                ++ncomp;
-            }
-        } else {
-            bp_parent_t[base + nlive] = parent;
-            bp_token_t[base + nlive] = pool_tok[p];
-            slot_score[base + nlive] = pool_model[p];
-            chosen[nc++] = pool_tok[p];
-            ++nlive;
-        }
-    }
-    *n_chosen = nc;
-    st[BS_STEPS] = steps + 1;
-    st[BS_NCOMP] = ncomp;
-    st[BS_NLIVE] = nlive;
-    st[BS_DONE] = ncomp >= g || steps + 1 >= max_time_step;
-    return !st[BS_DONE] && nlive > 0;
+    return place_cut(q * g, g, k, min_time_step, max_time_step, order, m, pool_model, pool_tok, pool_flag, t,
+                     state + (int64_t)q * BS_WORDS, bp_parent_t, bp_token_t, slot_score, comp_step, comp_parent, comp_score,
+                     ChosenHook{pool_tok, chosen, n_chosen});
 }
 
 // The whole advance of one graph by one thread (the host check; the kernel parallelises each group's pool and ranks).  pool_* are

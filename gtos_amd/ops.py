@@ -1335,20 +1335,35 @@ def beam_topk(ll, k):
     return val, idx
 
 
-def beam_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state,
-                 bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
-    """One advance of every beam at step t (gtos_beam_advance): updates slot_score, beam_state, bp_* row t, comp_*, active in place."""
-    B = beam_state.shape[0]
+def _check_beam_tables(k, groups, V, tot, max_time_step, topv, topi, flag_shared, flag_local, slot_score, state, bp_parent, bp_token,
+                       comp_step, comp_parent, comp_score, active):
+    """The plain tables every *_advance takes (BeamTables in csrc/beam_device.h), each for shape, dtype and contiguity: topv fp32 /
+    topi int32 [N, k], the uint8 token classes, slot_score fp64 [N], state int32 with one row of 4 words per group (``groups`` per
+    graph; 1: per beam), bp_parent / bp_token int32 [max_time_step, N], comp_step / comp_parent int32 and comp_score fp64 [B, k],
+    active int32 [3].  -> B, N"""
+    B = state.numel() // (4 * groups)
     N = B * k
-    require_cuda(topv, topi, flag_shared, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active)
+    assert state.dtype == torch.int32 and tuple(state.shape) in ((B * groups, 4), (B, groups, 4))
+    require_cuda(topv, topi, flag_shared, slot_score, state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active)
     assert topv.shape == (N, k) and topi.shape == (N, k) and topv.dtype == torch.float32 and topi.dtype == torch.int32
     assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
     assert flag_local is None or (flag_local.dtype == torch.uint8 and flag_local.numel() >= B * (tot - V))
-    assert slot_score.dtype == torch.float64 and slot_score.numel() == N and beam_state.shape == (B, 4)
-    assert bp_parent.shape == (max_time_step, N) and bp_token.shape == (max_time_step, N)
-    assert comp_step.shape == (B, k) and comp_parent.shape == (B, k) and comp_score.shape == (B, k) and active.numel() == 3
-    for x in (topv, topi, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
+    assert slot_score.dtype == torch.float64 and slot_score.numel() == N
+    for x in (bp_parent, bp_token):
+        assert x.shape == (max_time_step, N) and x.dtype == torch.int32
+    for x, dtype in ((comp_step, torch.int32), (comp_parent, torch.int32), (comp_score, torch.float64)):
+        assert x.shape == (B, k) and x.dtype == dtype
+    assert active.numel() == 3 and active.dtype == torch.int32
+    for x in (topv, topi, flag_shared, flag_local, slot_score, state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
         assert x is None or x.is_contiguous()
+    return B, N
+
+
+def beam_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state,
+                 bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
+    """One advance of every beam at step t (gtos_beam_advance): updates slot_score, beam_state, bp_* row t, comp_*, active in place."""
+    B, N = _check_beam_tables(k, 1, V, tot, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token,
+                              comp_step, comp_parent, comp_score, active)
     call("gtos_beam_advance", B, k, t, V, tot, min_time_step, max_time_step, ptr(topv), ptr(topi), ptr(flag_shared), ptr(flag_local),
          ptr(slot_score), ptr(beam_state), ptr(bp_parent), ptr(bp_token), ptr(comp_step), ptr(comp_parent), ptr(comp_score),
          ptr(active), stream())
@@ -1359,18 +1374,9 @@ def diverse_advance(t, k, groups, diversity, V, tot, min_time_step, max_time_ste
     """One advance of every graph's ``groups`` groups at step t (gtos_diverse_advance, the rule of csrc/diverse_kernels.h): beam_advance
     with group_state int32 [B*groups, 4] (or [B, groups, 4]) and the fp64 penalty weight ``diversity``; the other tables as there."""
     import struct
-    assert groups >= 1 and k % groups == 0 and group_state.numel() % (4 * groups) == 0
-    B = group_state.numel() // (4 * groups)
-    N = B * k
-    require_cuda(topv, topi, flag_shared, slot_score, group_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active)
-    assert topv.shape == (N, k) and topi.shape == (N, k) and topv.dtype == torch.float32 and topi.dtype == torch.int32
-    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
-    assert flag_local is None or (flag_local.dtype == torch.uint8 and flag_local.numel() >= B * (tot - V))
-    assert slot_score.dtype == torch.float64 and slot_score.numel() == N and group_state.shape[-1] == 4 and group_state.dtype == torch.int32
-    assert bp_parent.shape == (max_time_step, N) and bp_token.shape == (max_time_step, N)
-    assert comp_step.shape == (B, k) and comp_parent.shape == (B, k) and comp_score.shape == (B, k) and active.numel() == 3
-    for x in (topv, topi, flag_shared, flag_local, slot_score, group_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, active):
-        assert x is None or x.is_contiguous()
+    assert groups >= 1 and k % groups == 0
+    B, N = _check_beam_tables(k, groups, V, tot, max_time_step, topv, topi, flag_shared, flag_local, slot_score, group_state, bp_parent,
+                              bp_token, comp_step, comp_parent, comp_score, active)
     bits = struct.unpack("<Q", struct.pack("<d", float(diversity)))[0]
     call("gtos_diverse_advance", B, k, groups, bits, t, V, tot, min_time_step, max_time_step, ptr(topv), ptr(topi), ptr(flag_shared),
          ptr(flag_local), ptr(slot_score), ptr(group_state), ptr(bp_parent), ptr(bp_token), ptr(comp_step), ptr(comp_parent),
@@ -1386,23 +1392,14 @@ def constrain_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, ll
     beam_advance with ll [N, tot] fp32 (unit column stride; read for the forced candidates), cons int32 [B, Cw] (each graph's constraint
     ids, then -1; Cw <= CONSTRAIN_MAX, 0 allowed) and met int32 [2, N] (the slots' masks, rows alternating by step parity); the other
     tables as there."""
-    B = beam_state.shape[0]
-    N = B * k
-    require_cuda(topv, topi, ll, cons, flag_shared, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, met, active)
+    B, N = _check_beam_tables(k, 1, V, tot, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token,
+                              comp_step, comp_parent, comp_score, active)
+    require_cuda(ll, cons, met)
     if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1 or ll.shape != (N, tot):
         raise _lib.GtosHipError("constrain_advance: ll must be an [N, tot] fp32 tensor with unit column stride")
-    assert cons.dim() == 2 and cons.shape[0] == B and cons.shape[1] <= CONSTRAIN_MAX and cons.dtype == torch.int32
+    assert cons.dim() == 2 and cons.shape[0] == B and cons.shape[1] <= CONSTRAIN_MAX and cons.dtype == torch.int32 and cons.is_contiguous()
     Cw = cons.shape[1]
-    assert met.shape == (2, N) and met.dtype == torch.int32
-    assert topv.shape == (N, k) and topi.shape == (N, k) and topv.dtype == torch.float32 and topi.dtype == torch.int32
-    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
-    assert flag_local is None or (flag_local.dtype == torch.uint8 and flag_local.numel() >= B * (tot - V))
-    assert slot_score.dtype == torch.float64 and slot_score.numel() == N and beam_state.shape == (B, 4) and beam_state.dtype == torch.int32
-    assert bp_parent.shape == (max_time_step, N) and bp_token.shape == (max_time_step, N)
-    assert comp_step.shape == (B, k) and comp_parent.shape == (B, k) and comp_score.shape == (B, k) and active.numel() == 3
-    for x in (topv, topi, cons, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, met,
-              active):
-        assert x is None or x.is_contiguous()
+    assert met.shape == (2, N) and met.dtype == torch.int32 and met.is_contiguous()
     call("gtos_constrain_advance", B, k, Cw, t, V, tot, min_time_step, max_time_step, ptr(topv), ptr(topi), ptr(ll), max(ll.stride(0), tot),
          ptr(cons) if Cw else None, ptr(flag_shared), ptr(flag_local), ptr(slot_score), ptr(beam_state), ptr(bp_parent), ptr(bp_token),
          ptr(comp_step), ptr(comp_parent), ptr(comp_score), ptr(met), ptr(active), stream())
@@ -1435,25 +1432,17 @@ def coverage_advance(t, k, beta, V, tot, min_time_step, max_time_step, topv, top
     coverage_step), which also records per surviving slot slot_cp fp64 [N] / slot_cov fp32 [N, n] and per completion comp_cp fp64
     [B, k] / comp_cov fp32 [B, k, n]; the other tables as there."""
     import struct
-    B = beam_state.shape[0]
-    N = B * k
-    require_cuda(topv, topi, flag_shared, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, cp, cov_cur,
-                 slot_cp, comp_cp, comp_cov, slot_cov, active)
+    B, N = _check_beam_tables(k, 1, V, tot, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token,
+                              comp_step, comp_parent, comp_score, active)
+    require_cuda(cp, cov_cur, slot_cp, comp_cp, comp_cov, slot_cov)
     assert isinstance(beta, float) and 0 <= beta < float('inf')
     assert cov_cur.dim() == 2 and cov_cur.shape[0] == N and cov_cur.shape[1] >= 1 and cov_cur.dtype == torch.float32
     n = cov_cur.shape[1]
     assert cp.dtype == torch.float64 and cp.numel() == N and slot_cp.dtype == torch.float64 and slot_cp.numel() == N
     assert comp_cp.dtype == torch.float64 and comp_cp.shape == (B, k)
     assert comp_cov.shape == (B, k, n) and comp_cov.dtype == torch.float32 and slot_cov.shape == (N, n) and slot_cov.dtype == torch.float32
-    assert topv.shape == (N, k) and topi.shape == (N, k) and topv.dtype == torch.float32 and topi.dtype == torch.int32
-    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
-    assert flag_local is None or (flag_local.dtype == torch.uint8 and flag_local.numel() >= B * (tot - V))
-    assert slot_score.dtype == torch.float64 and slot_score.numel() == N and beam_state.shape == (B, 4) and beam_state.dtype == torch.int32
-    assert bp_parent.shape == (max_time_step, N) and bp_token.shape == (max_time_step, N)
-    assert comp_step.shape == (B, k) and comp_parent.shape == (B, k) and comp_score.shape == (B, k) and active.numel() == 3
-    for x in (topv, topi, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, cp,
-              cov_cur, slot_cp, comp_cp, comp_cov, slot_cov, active):
-        assert x is None or x.is_contiguous()
+    for x in (cp, cov_cur, slot_cp, comp_cp, comp_cov, slot_cov):
+        assert x.is_contiguous()
     bits = struct.unpack("<Q", struct.pack("<d", beta))[0]
     call("gtos_coverage_advance", B, k, t, V, tot, min_time_step, max_time_step, bits, n, ptr(topv), ptr(topi), ptr(flag_shared),
          ptr(flag_local), ptr(slot_score), ptr(beam_state), ptr(bp_parent), ptr(bp_token), ptr(comp_step), ptr(comp_parent),

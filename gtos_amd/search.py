@@ -71,19 +71,26 @@ class Beam(object):
             for token, ll in steps:
                 pool.append((parent, token, float('-inf') if token == UNK else base + ll))
         pool.sort(key=lambda c: c[2], reverse=True)                     # stable: ties keep (parent, rank) order
-        pool = pool[:self.beam_size - len(self.completed_hypotheses)]
-        alive, parents = [], []
-        for parent, token, score in pool:
-            hyp = Hypothesis(self.hypotheses[parent].seq + [token], score)
+        return [c[0] for c in self.place(pool)]
+
+    def place(self, ranked, make=lambda parent, seq, score: Hypothesis(seq, score)):
+        """The placement every selection rule ends with (place_cut in csrc/beam_kernels.h).  ranked: the whole pool in its final order,
+        entries (parent, token, score, ...).  Cuts it to ``beam_size - #finished``; in that order a continuation ending in <END> finishes
+        its hypothesis (kept only if it has at least ``min_time_step`` tokens) and any other one is the next live hypothesis, built by
+        make(parent, seq, score); counts the step.  Returns the entries that stay alive, in their new order."""
+        alive, kept = [], []
+        for c in ranked[:self.beam_size - len(self.completed_hypotheses)]:
+            parent, token, score = c[:3]
+            hyp = make(parent, self.hypotheses[parent].seq + [token], score)
             if hyp.is_completed():
                 if len(hyp) - 2 >= self.min_time_step:
                     self.completed_hypotheses.append(hyp)
             else:
                 alive.append(hyp)
-                parents.append(parent)
+                kept.append(c)
         self.hypotheses = alive
         self.steps += 1
-        return parents
+        return kept
 
     def completed(self):
         return len(self.completed_hypotheses) >= self.beam_size or self.steps >= self.max_time_step
@@ -136,20 +143,9 @@ class GroupBeam(Beam):
                     score = float('-inf') if token == UNK else base + ll
                     pool.append((parent, token, score, score - self.diversity * chosen.count(token)))
             pool.sort(key=lambda c: c[3], reverse=True)                 # stable: ties keep (parent, rank) order
-            pool = pool[:grp.beam_size - len(grp.completed_hypotheses)]
-            alive, parents = [], []
-            for parent, token, score, _ in pool:
-                hyp = Hypothesis(grp.hypotheses[parent].seq + [token], score)
-                if hyp.is_completed():
-                    if len(hyp) - 2 >= grp.min_time_step:
-                        grp.completed_hypotheses.append(hyp)
-                else:
-                    alive.append(hyp)
-                    parents.append(parent)
-                    chosen.append(token)
-            grp.hypotheses = alive
-            grp.steps += 1
-            self.last_parents[j] = parents
+            kept = grp.place(pool)
+            chosen.extend(token for _, token, _, _ in kept)             # no one reads the list before the next group does
+            self.last_parents[j] = parents = [c[0] for c in kept]
             if not grp.completed():
                 keep.extend(pos + p for p in parents)
             pos += n
@@ -209,19 +205,9 @@ class ConstrainedBeam(Beam):
             cands.sort(key=lambda c: c[2], reverse=True)                # stable: ties keep pool order
             ranked.extend((q, -bank, c) for q, c in enumerate(cands))
         ranked.sort(key=lambda x: x[:2])                                # (q, bank) is unique
-        alive, parents, met = [], [], []
-        for _, _, (parent, token, score, mask) in ranked[:self.beam_size - len(self.completed_hypotheses)]:
-            hyp = Hypothesis(self.hypotheses[parent].seq + [token], score)
-            if hyp.is_completed():
-                if len(hyp) - 2 >= self.min_time_step:
-                    self.completed_hypotheses.append(hyp)
-            else:
-                alive.append(hyp)
-                parents.append(parent)
-                met.append(mask)
-        self.hypotheses, self.met = alive, met
-        self.steps += 1
-        return parents
+        kept = self.place([c for _, _, c in ranked])
+        self.met = [mask for _, _, _, mask in kept]
+        return [c[0] for c in kept]
 
 
 class CoveredHypothesis(Hypothesis):
@@ -255,19 +241,7 @@ class CoverageBeam(Beam):
                 score = float('-inf') if token == UNK else base + ll
                 pool.append((parent, token, score, score + self.beta * cp[parent]))
         pool.sort(key=lambda c: c[3], reverse=True)                     # stable: ties keep (parent, rank) order
-        pool = pool[:self.beam_size - len(self.completed_hypotheses)]
-        alive, parents = [], []
-        for parent, token, score, _ in pool:
-            hyp = CoveredHypothesis(self.hypotheses[parent].seq + [token], score, cp[parent], coverage[parent])
-            if hyp.is_completed():
-                if len(hyp) - 2 >= self.min_time_step:
-                    self.completed_hypotheses.append(hyp)
-            else:
-                alive.append(hyp)
-                parents.append(parent)
-        self.hypotheses = alive
-        self.steps += 1
-        return parents
+        return [c[0] for c in self.place(pool, lambda parent, seq, score: CoveredHypothesis(seq, score, cp[parent], coverage[parent]))]
 
     def get_k_best(self, k, alpha):
         if not self.completed_hypotheses:
@@ -494,6 +468,47 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     return fill(beams, k, token_string=lambda b, i: local[b][i] if i in local[b] else pv.idx2token(i), **host)
 
 
+def _plain_cuts(d, rows, ints=(), dbls=()):
+    """The int32 and fp64 cuts (a layout() result) of the tables every beam route keeps, in the format fill_beams reads: ``rows`` state
+    rows of (steps, #completed, #live, done) with slot 0 live, the back-pointer rows and the completion tables; then the route's own."""
+    return ([('state', (rows, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
+             ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0)] + list(ints),
+            [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0)] + list(dbls))
+
+
+def _plain_tables(d):
+    """The tables of _plain_cuts as every ops.*_advance takes them after topv / topi, up to ``active``"""
+    a, tab = d.arr, d.tab
+    return (tab['flag_shared'], tab['flag_local'], a['slot_score'], a['state'], a['bp_parent'], a['bp_token'], a['comp_step'],
+            a['comp_parent'], a['comp_score'])
+
+
+def _plain_reorder(d, t, cur, nxt, tok_out, char_out, width=None):
+    """The reorder that ends a step of every beam route: gtos_beam_reorder, or gtos_diverse_reorder for groups of ``width`` slots"""
+    a, tab = d.arr, d.tab
+    rest = (a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'], tab['tok_local'], tab['char_shared'],
+            tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+    if width is None:
+        ops.beam_reorder(cur, nxt, t, d.k, *rest)
+    else:
+        ops.diverse_reorder(cur, nxt, t, d.k, width, *rest)
+
+
+def _taken(d, t):
+    """_slot_decode's ``taken`` of every beam route: row t of the back-pointer tables"""
+    return d.arr['bp_parent'][t], d.arr['bp_token'][t]
+
+
+def _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill, live0=1, fresh=None, **more):
+    """_slot_decode for a beam route (two cache copies, _taken); a beam no step ran for (max_time_step <= 0) is then left as the
+    route's fill leaves a beam: fresh(beam)."""
+    _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, live0, layout, step, fill, no_repeat_ngram, _taken, **more)
+    for beam in beams:
+        if fresh is not None and beam.steps == 0:
+            fresh(beam)
+    return beams
+
+
 def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0, groups=1, diversity=0.0, grouped=None,
                        constraints=None, constrained=None, coverage=None, covered=None):
     """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
@@ -530,19 +545,11 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat
     if grouped:
         return _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, groups, float(diversity))
 
-    def layout(d):
-        return ([('state', (d.B, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
-                 ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0)], [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0)])
-
     def step(d, t, ll, cur, nxt, tok_out, char_out):
-        a, tab = d.arr, d.tab
         topv, topi = ops.beam_topk(ll, d.k)
-        ops.beam_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, topv, topi, tab['flag_shared'], tab['flag_local'], a['slot_score'],
-                         a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'], a['active'])
-        ops.beam_reorder(cur, nxt, t, d.k, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
-                         tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
-    return _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill_beams, no_repeat_ngram,
-                        lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]))
+        ops.beam_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, topv, topi, *_plain_tables(d), d.arr['active'])
+        _plain_reorder(d, t, cur, nxt, tok_out, char_out)
+    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, lambda d: _plain_cuts(d, d.B), step, fill_beams)
 
 
 def _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, G, diversity):
@@ -552,25 +559,14 @@ def _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngra
         assert G >= 1 and beams[0].beam_size % G == 0 and 0 <= diversity < float('inf'), "groups divide the beam size; diversity is finite and >= 0"
         g = beams[0].beam_size // G
 
-    def layout(d):
-        return ([('state', (d.B * G, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
-                 ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0)], [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0)])
-
     def step(d, t, ll, cur, nxt, tok_out, char_out):
-        a, tab = d.arr, d.tab
         topv, topi = ops.beam_topk(ll, d.k)
-        ops.diverse_advance(t, d.k, G, diversity, d.V, d.tot, d.min_t, d.max_t, topv, topi, tab['flag_shared'], tab['flag_local'],
-                            a['slot_score'], a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'],
-                            a['active'])
-        ops.diverse_reorder(cur, nxt, t, d.k, g, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
-                            tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+        ops.diverse_advance(t, d.k, G, diversity, d.V, d.tot, d.min_t, d.max_t, topv, topi, *_plain_tables(d), d.arr['active'])
+        _plain_reorder(d, t, cur, nxt, tok_out, char_out, width=g)
     fill = lambda beams_, k, **tables: fill_beams(beams_, k, groups=G, **tables)
-    _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, (g, 1) if beams else 1, layout, step, fill,
-                 no_repeat_ngram, lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]))
-    for beam in beams:
-        if getattr(beam, 'groups', None) is None:            # no step ran (max_time_step <= 0): fresh groups
-            gather_groups(beam, [Beam(g, beam.min_time_step, beam.max_time_step) for _ in range(G)])
-    return beams
+    fresh = lambda beam: gather_groups(beam, [Beam(g, beam.min_time_step, beam.max_time_step) for _ in range(G)])
+    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, lambda d: _plain_cuts(d, d.B * G), step, fill,
+                       live0=(g, 1) if beams else 1, fresh=fresh)
 
 
 def _constrained_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, constraints):
@@ -586,18 +582,12 @@ def _constrained_search_device(model, memory, beams, sync_every, stats, no_repea
         if width > ops.CONSTRAIN_MAX or any(not 0 <= i < d.tot for x in ids for i in x):
             raise ValueError("constraints: at most %d per graph, each an output id of the batch" % ops.CONSTRAIN_MAX)
         d.cons = torch.tensor([x + [-1] * (width - len(x)) for x in ids], dtype=torch.int32).view(d.B, width).to(memory['probe'].device)
-        return ([('state', (d.B, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
-                 ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0), ('met', (2, d.N), 0)],
-                [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0)])
+        return _plain_cuts(d, d.B, ints=[('met', (2, d.N), 0)])
 
     def step(d, t, ll, cur, nxt, tok_out, char_out):
-        a, tab = d.arr, d.tab
         topv, topi = ops.beam_topk(ll, d.k)
-        ops.constrain_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, topv, topi, ll, d.cons, tab['flag_shared'], tab['flag_local'],
-                              a['slot_score'], a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'],
-                              a['met'], a['active'])
-        ops.beam_reorder(cur, nxt, t, d.k, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
-                         tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+        ops.constrain_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, topv, topi, ll, d.cons, *_plain_tables(d), d.arr['met'], d.arr['active'])
+        _plain_reorder(d, t, cur, nxt, tok_out, char_out)
 
     def fill(beams_, k, met, state, **tables):
         fill_beams(beams_, k, state=state, **tables)
@@ -606,12 +596,8 @@ def _constrained_search_device(model, memory, beams, sync_every, stats, no_repea
             steps, nlive = state[4 * b], state[4 * b + 2]
             beam.met = [met[(steps % 2) * N + b * k + j] for j in range(nlive)] if steps else [0]
         return beams_
-    _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill, no_repeat_ngram,
-                 lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]))
-    for beam in beams:
-        if getattr(beam, 'met', None) is None:               # no step ran (max_time_step <= 0)
-            beam.met = [0]
-    return beams
+    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill,
+                       fresh=lambda beam: setattr(beam, 'met', [0]))
 
 
 def _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, beta):
@@ -631,19 +617,15 @@ def _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ng
         c.cp = torch.zeros(d.N, dtype=torch.float64, device=dev)
         c.slot_cov = torch.zeros((d.N, n), dtype=torch.float32, device=dev)
         c.comp_cov = torch.zeros((d.B, d.k, n), dtype=torch.float32, device=dev)
-        return ([('state', (d.B, 4), (0, 0, 1, 0)), ('bp_parent', (d.max_t, d.N), -1), ('bp_token', (d.max_t, d.N), -1),
-                 ('comp_step', (d.B, d.k), 0), ('comp_parent', (d.B, d.k), 0)],
-                [('slot_score', (d.N,), 0), ('comp_score', (d.B, d.k), 0), ('slot_cp', (d.N,), 0), ('comp_cp', (d.B, d.k), 0)])
+        return _plain_cuts(d, d.B, dbls=[('slot_cp', (d.N,), 0), ('comp_cp', (d.B, d.k), 0)])
 
     def step(d, t, ll, cur, nxt, tok_out, char_out):
-        a, tab, c = d.arr, d.tab, tables
+        a, c = d.arr, tables
         ops.coverage_step(t, d.k, d.align, c.pad, a['bp_parent'][t - 1] if t else None, c.cov[(t + 1) % 2], c.cov[t % 2], c.cp, a['active'])
         topv, topi = ops.beam_topk(ll, d.k)
-        ops.coverage_advance(t, d.k, beta, d.V, d.tot, d.min_t, d.max_t, topv, topi, tab['flag_shared'], tab['flag_local'], a['slot_score'],
-                             a['state'], a['bp_parent'], a['bp_token'], a['comp_step'], a['comp_parent'], a['comp_score'], c.cp,
-                             c.cov[t % 2], a['slot_cp'], a['comp_cp'], c.comp_cov, c.slot_cov, a['active'])
-        ops.beam_reorder(cur, nxt, t, d.k, a['bp_parent'], a['bp_token'], a['state'], a['active'], d.V, d.tot, tab['tok_shared'],
-                         tab['tok_local'], tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
+        ops.coverage_advance(t, d.k, beta, d.V, d.tot, d.min_t, d.max_t, topv, topi, *_plain_tables(d), c.cp, c.cov[t % 2], a['slot_cp'],
+                             a['comp_cp'], c.comp_cov, c.slot_cov, a['active'])
+        _plain_reorder(d, t, cur, nxt, tok_out, char_out)
 
     def fill(beams_, k, slot_cp, comp_cp, state, **plain):
         c, N = tables, len(beams_) * k
@@ -657,12 +639,8 @@ def _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ng
                                          for j, h in enumerate(beam.completed_hypotheses)]
             beam.hypotheses = [CoveredHypothesis(h.seq, h.score, slot_cp[b * k + j], rows[b * k + j]) for j, h in enumerate(beam.hypotheses)]
         return beams_
-    _slot_decode("beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill, no_repeat_ngram,
-                 lambda d, t: (d.arr['bp_parent'][t], d.arr['bp_token'][t]), want_align=True, extra_reads=1)
-    for beam in beams:
-        if beam.steps == 0:                                  # no step ran (max_time_step <= 0)
-            beam.hypotheses = [CoveredHypothesis([STR], 0., 0., [])]
-    return beams
+    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill, want_align=True, extra_reads=1,
+                       fresh=lambda beam: setattr(beam, 'hypotheses', [CoveredHypothesis([STR], 0., 0., [])]))
 
 
 def slot_memory(memory, B, k):
