@@ -158,3 +158,106 @@ def assert_bound(name, got, ref, S, cacc, cout, extra=None):
     ratio, err = bound_ratio(got, ref, S, cacc, cout, extra)
     print("MEASURED %s: max |err| %.3e, max err/bound %.3e (c_acc %.2e, c_out %.2e)" % (name, err, ratio, cacc, cout))
     assert ratio <= 1.0, "%s: error %.3e exceeds the bound by %.2fx" % (name, err, ratio)
+
+
+# ------------------------------------------------------------------------------------------------ GRU step kernels: fp64 and bounds
+# The step kernels (csrc/gru_step.hip, the unfused cells of csrc/rowops.hip) against float64 restatements of one time step, every error
+# propagated to first order from three constants and no free tolerance:
+#   c_acc(K) * S     an fp32 accumulation of K terms whose absolute values sum to S (products, bias and elementwise additions),
+#   C_OUT[dtype]     half an ulp of a stored output, relative to its value,
+#   c_fast(pre)      __expf / v_rcp_f32 behind a sigmoid or the fast tanh: 1-ulp hardware exp2 and rcp plus the rounding of the scaled
+#                    argument, which grows with the pre-activation: 32 eps (1 + |pre|).
+# With u the first-order error of a value BEFORE it is rounded to its stored type, the stored value is held to
+# C_OUT |ref| + (1 + C_OUT) u: the half ulp is taken of the computed value, which may exceed |ref| by u.
+def c_fast(pre):
+    return 32.0 * EPS32 * (1.0 + pre.abs())
+
+
+def within_ratio(got, ref, bound):
+    """max over elements of |got - ref| / bound (NaN anywhere -> inf) and the largest error"""
+    err = (got.double() - ref).abs()
+    r = err / (bound + 1e-30)
+    if bool(torch.isnan(r).any()):
+        return float("inf"), float("nan")
+    if r.numel() == 0:
+        return 0.0, 0.0
+    return float(r.max()), float(err.max())
+
+
+def assert_within(name, got, ref, bound):
+    ratio, err = within_ratio(got, ref, bound)
+    print("MEASURED %s: max |err| %.3e, max err/bound %.3e" % (name, err, ratio))
+    assert ratio <= 1.0, "%s: error %.3e exceeds the bound by %.2fx" % (name, err, ratio)
+
+
+def stored_bound(ref, u, dtype):
+    return C_OUT[dtype] * ref.abs() + (1.0 + C_OUT[dtype]) * u
+
+
+def drop_scale(p):
+    """1 / (1 - p) of the fp32 p the kernels are handed"""
+    return 1.0 / (1.0 - float(torch.tensor(p, dtype=torch.float32))) if p > 0 else 1.0
+
+
+def gru_fwd_bounds(xg, Sx, hg, Sh, h, hn_stored, K, dtype, keep=None, p=0.0):
+    """One forward step in float64.  ``xg`` / ``hg`` [rows, 3hs]: the input and recurrent gate pre-activations WITH their biases, from the
+    stored operands; ``Sx`` / ``Sh``: the same sums over absolute values; ``h`` [rows, hs]: the entering state; ``hn_stored``: the
+    kernel's own stored hn = hg_n (the kernel rounds it to the stored type before it uses it, for backward's sake: n and h' are
+    restated from that value, hn itself is held to the fp64 product); ``K``: terms per pre-activation; ``keep``: the dropout mask of y.
+    Returns {name: (ref, bound)} for r, z, hn, n, h, y -- the bounds are those of values stored as ``dtype``."""
+    hs = h.shape[1]
+    ca = c_acc(K)
+
+    def blk(t, g):
+        return t[:, g * hs:(g + 1) * hs]
+    ref, u = {}, {}
+    for g, name in enumerate("rz"):
+        pre = blk(xg, g) + blk(hg, g)
+        ref[name] = torch.sigmoid(pre)
+        u[name] = ca * (blk(Sx, g) + blk(Sh, g)) / 4 + c_fast(pre)            # |sigmoid'| <= 1/4
+    ref["hn"], u["hn"] = blk(hg, 2), ca * blk(Sh, 2)
+    hn = hn_stored.double()
+    r, z = ref["r"], ref["z"]
+    pre_n = blk(xg, 2) + r * hn
+    n = ref["n"] = torch.tanh(pre_n)
+    u["n"] = ca * (blk(Sx, 2) + (r * hn).abs()) + hn.abs() * u["r"] + c_fast(pre_n)          # |tanh'| <= 1
+    ref["h"] = (1 - z) * n + z * h
+    u["h"] = u["z"] * (h - n).abs() + (1 - z) * u["n"] + c_acc(1) * (((1 - z) * n).abs() + (z * h).abs())
+    ks = drop_scale(p)
+    keep = torch.ones_like(h) if keep is None else keep.double()
+    ref["y"] = keep * ref["h"] * ks
+    u["y"] = keep * ks * u["h"] + c_acc(1) * ref["y"].abs()                    # 1 / (1 - p) and the product in fp32
+    return {k: (ref[k], stored_bound(ref[k], u[k], dtype)) for k in ref}
+
+
+def gru_bwd_bounds(gates, hp, g_in, S_in, P, S_P, K, d4_dtype, dh_dtype):
+    """One backward step of the cell in float64.  ``gates`` [rows, 4hs] = (r | z | n | hn) and ``hp`` [rows, hs] as stored;
+    ``g_in`` = dh + drop(dy) and ``S_in`` = |dh| + |drop(dy)|; ``P`` / ``S_P``: the recurrent product
+    d4_prev[src][:, {0:2hs, 3hs:4hs}] @ wh_t^T and its sum over absolute values (zero rows where there is none); ``K`` its depth.
+    The error of g = g_in + P, c_acc(K) (S_in + S_P), reaches every output times the elementwise factor that multiplies g; the factors
+    are exact functions of stored values up to fp32 roundings (8 eps of the result; 1 - n^2 cancels: eps n^2 absolute).
+    Returns {name: (ref, bound)} for dr, dz, dn, dhn (the four blocks of d4) and dh (= g z)."""
+    hs = hp.shape[1]
+    gr, gz, gn, hn = (gates[:, i * hs:(i + 1) * hs].double() for i in range(4))
+    hp = hp.double()
+    g = g_in + P
+    e_g = c_acc(K) * (S_in + S_P)
+    q = 1 - gn * gn
+    fac = {"dn": (1 - gz) * q, "dz": (hp - gn) * gz * (1 - gz), "dh": gz}
+    fac["dhn"] = fac["dn"] * gr
+    fac["dr"] = fac["dn"] * hn * gr * (1 - gr)
+    noq = {"dn": (1 - gz), "dhn": (1 - gz) * gr, "dr": (1 - gz) * hn * gr * (1 - gr)}     # the factor without 1 - n^2
+    out = {}
+    for k, f in fac.items():
+        ref = g * f
+        u = e_g * f.abs() + 8 * EPS32 * ref.abs()
+        if k in noq:
+            u = u + EPS32 * gn * gn * (g * noq[k]).abs()
+        out[k] = (ref, stored_bound(ref, u, dh_dtype if k == "dh" else d4_dtype))
+    return out
+
+
+def bias_sum_bound(d4_stored, rows):
+    """(fp64 column sums of the stored d4 rows, c_acc(rows) * column sums of |d4|)"""
+    d = d4_stored.double()
+    return d.sum(0), c_acc(rows) * d.abs().sum(0)
