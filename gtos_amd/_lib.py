@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgtos_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 c_p, c_i, c_l, c_f, c_u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
 
@@ -76,6 +76,7 @@ SIGNATURES = {
     "gtos_diverse_reorder": [c_i, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_l, c_p,
                              c_p, c_p, c_p],
     "gtos_constrain_advance": [c_i] * 8 + [c_p, c_p, c_p, c_l] + [c_p] * 13,
+    "gtos_phrase_advance": [c_i] * 9 + [c_p, c_p, c_p, c_l] + [c_p] * 13,
     "gtos_coverage_step": [c_i] * 4 + [c_p] * 8,
     "gtos_coverage_advance": [c_i] * 7 + [c_u64, c_i] + [c_p] * 19,
     "gtos_highway_fwd": [c_i, c_l, c_i, c_p, c_p, c_p, c_p],

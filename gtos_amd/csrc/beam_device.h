@@ -1,5 +1,5 @@
 // What every advance entry point of the device-resident beam searches shares, for the .hip files only (csrc/beam.hip, diverse.hip,
-// constrain.hip, coverage.hip): the plain tables with their sizes as one struct that the four argument structs embed, its range and
+// constrain.hip, coverage.hip, phrase.hip): the plain tables with their sizes as one struct that the argument structs embed, its range and
 // null checks, and the kernels' guard on the state words they size their pools by.
 #pragma once
 #include "beam_kernels.h"

@@ -104,6 +104,53 @@ def check_constraints(constraints, search, groups, local_idx2token, vocab):
     return out
 
 
+def check_phrases(phrases, search, groups, constraints, coverage_penalty, local_idx2token, vocab):
+    """The argument checks of Generator.work(phrases=): None passes as None.  Otherwise ValueError unless the search is a beam search
+    without groups, constraints or coverage penalty and ``phrases`` holds, per graph of ``local_idx2token`` (the batch's copy tables),
+    a list of at most ops.PHRASE_MAX phrases of at most ops.PHRASE_TOKENS_MAX tokens together, a phrase being a non-empty list or tuple
+    of at most ops.PHRASE_LEN_MAX token strings (never a bare string), none of them <PAD>, <STR>, <END> or <UNK>, each producible for
+    its graph as in check_constraints.  A phrase may be listed twice.  -> a list of lists of lists."""
+    if phrases is None:
+        return None
+    if search == "sample":
+        raise ValueError("phrases apply to the beam searches, not to search='sample'")
+    if groups != 1:
+        raise ValueError("phrases do not combine with groups (got groups = %r)" % (groups,))
+    if constraints is not None:
+        raise ValueError("phrases do not combine with constraints: state a single token as a phrase of one")
+    if coverage_penalty is not None:
+        raise ValueError("phrases do not combine with coverage_penalty")
+    if isinstance(phrases, str) or not isinstance(phrases, (list, tuple)) or len(phrases) != len(local_idx2token):
+        raise ValueError("phrases holds one list of phrases per graph: %d graphs, got %r"
+                         % (len(local_idx2token), phrases if not isinstance(phrases, (list, tuple)) else len(phrases)))
+    out = []
+    for b, (entry, local) in enumerate(zip(phrases, local_idx2token)):
+        if isinstance(entry, str) or not isinstance(entry, (list, tuple)):
+            raise ValueError("phrases[%d] is a list of phrases, got %r" % (b, entry))
+        if len(entry) > ops.PHRASE_MAX:
+            raise ValueError("phrases[%d]: at most %d phrases per graph, got %d" % (b, ops.PHRASE_MAX, len(entry)))
+        copies = set(local.values())
+        for phrase in entry:
+            if isinstance(phrase, str):
+                raise ValueError("phrases[%d]: a phrase is a list of token strings, got the bare string %r (write [%r])" % (b, phrase, phrase))
+            if not isinstance(phrase, (list, tuple)) or not phrase:
+                raise ValueError("phrases[%d]: a phrase is a non-empty list of token strings, got %r" % (b, phrase))
+            if len(phrase) > ops.PHRASE_LEN_MAX:
+                raise ValueError("phrases[%d]: at most %d tokens per phrase, got %d" % (b, ops.PHRASE_LEN_MAX, len(phrase)))
+            for w in phrase:
+                if not isinstance(w, str):
+                    raise ValueError("phrases[%d]: a phrase holds token strings, got %r" % (b, w))
+                if w in (PAD, STR, END, UNK):
+                    raise ValueError("phrases[%d]: %s cannot be part of a phrase" % (b, w))
+                if w not in copies and vocab.token2idx(w) == vocab.unk_idx:
+                    raise ValueError("phrases[%d]: %r is neither a copy token of the graph nor in the vocabulary" % (b, w))
+        if sum(len(phrase) for phrase in entry) > ops.PHRASE_TOKENS_MAX:
+            raise ValueError("phrases[%d]: at most %d tokens per graph, got %d"
+                             % (b, ops.PHRASE_TOKENS_MAX, sum(len(phrase) for phrase in entry)))
+        out.append([list(phrase) for phrase in entry])
+    return out
+
+
 def check_coverage(beta, search, groups, constraints):
     """The argument checks of Generator.work(coverage_penalty=): None passes as None.  Otherwise ValueError unless beta is a finite
     real >= 0 (0.0: the plain search with the coverage reported) and the search is a beam search without groups or constraints."""
@@ -259,7 +306,7 @@ class Generator(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ inference
     def work(self, data, beam_size, max_time_step, min_time_step=1, search="host", *, temperature=1.0, top_k=0, top_p=1.0,
-             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage_penalty=None):
+             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage_penalty=None, phrases=None):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
         step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
@@ -282,7 +329,13 @@ class Generator(nn.Module):
         log-likelihood plus beta * sum over the nodes of log(min(coverage, 1)) of its parent (gtos_amd.search.CoverageBeam, the rule of
         csrc/coverage_kernels.h; on the device by gtos_coverage_step / gtos_coverage_advance).  Scores stay log-likelihoods.  The
         returned beams are CoverageBeam objects -- ``get_k_best`` adds beta * cp to the length-normalised score -- of
-        CoveredHypothesis, each with ``cp`` and ``coverage`` (one float per node); 0.0 searches as without and reports them."""
+        CoveredHypothesis, each with ``cp`` and ``coverage`` (one float per node); 0.0 searches as without and reports them.
+        ``phrases`` ("host" and "device", groups = 1, no constraints, no coverage penalty): one list of phrases per graph (a list may
+        be empty), a phrase being a non-empty list of token strings that the output must hold as consecutive tokens -- ``constraints``
+        with constraints of several tokens (gtos_amd.search.PhraseBeam, the rule of csrc/phrase_kernels.h; on the device by
+        gtos_phrase_advance).  A phrase listed twice must occur twice; the strings resolve as for ``constraints`` (check_phrases).  A
+        returned beam then carries ``met``, the bit masks of the phrases its live hypotheses have finished, and ``progress``, per live
+        hypothesis (open, pos): the phrase in progress and its tokens matched so far, (-1, 0) when none is."""
         if search not in ("host", "device", "sample"):
             raise ValueError("search must be 'host', 'device' or 'sample', got %r" % (search,))
         no_repeat_ngram = check_no_repeat_ngram(no_repeat_ngram, search, max_time_step)
@@ -290,6 +343,9 @@ class Generator(nn.Module):
         coverage_penalty = check_coverage(coverage_penalty, search, groups, constraints)
         if constraints is not None:
             constraints = check_constraints(constraints, search, groups, data['local_idx2token'], self.vocabs['predictable_token'])
+        if phrases is not None:
+            phrases = check_phrases(phrases, search, groups, constraints, coverage_penalty, data['local_idx2token'],
+                                    self.vocabs['predictable_token'])
         if search == "sample":
             check_sampling(beam_size, temperature, top_k, top_p, seed)
             if seed is None:
@@ -320,6 +376,8 @@ class Generator(nn.Module):
             if coverage_penalty is not None:                                               # None: likewise
                 block.update(coverage=coverage_penalty)
                 beams = [CoverageBeam(beam_size, min_time_step, max_time_step, coverage_penalty) for _ in beams]
+            if phrases is not None:                                                        # None: likewise
+                block.update(phrases=phrases)
             if search == "device":
                 beam_search_device(self, memory, beams, **block)
             elif search == "sample":

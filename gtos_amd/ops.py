@@ -1405,6 +1405,32 @@ def constrain_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, ll
          ptr(comp_step), ptr(comp_parent), ptr(comp_score), ptr(met), ptr(active), stream())
 
 
+PHRASE_MAX = 16          # MAX_PHR of csrc/phrase_kernels.h: the phrases one graph may carry (one bit of a slot's state each)
+PHRASE_LEN_MAX = 16      # MAX_LEN: the tokens of one phrase
+PHRASE_TOKENS_MAX = 64   # MAX_TOKENS: the tokens of one graph's phrases together (the bank levels)
+
+
+def phrase_advance(t, k, V, tot, min_time_step, max_time_step, topv, topi, ll, phr, flag_shared, flag_local, slot_score, beam_state,
+                   bp_parent, bp_token, comp_step, comp_parent, comp_score, pst, active):
+    """One advance of every beam at step t under phrase constraints (gtos_phrase_advance, the rule of csrc/phrase_kernels.h):
+    constrain_advance with phr int32 [B, Cw, Lw] (each graph's phrases, each its ids and then -1; Cw <= PHRASE_MAX, Lw <=
+    PHRASE_LEN_MAX, Cw = 0 allowed) and pst int32 [2, N] (the slots' packed states, rows alternating by step parity); the other tables
+    as there."""
+    B, N = _check_beam_tables(k, 1, V, tot, max_time_step, topv, topi, flag_shared, flag_local, slot_score, beam_state, bp_parent, bp_token,
+                              comp_step, comp_parent, comp_score, active)
+    require_cuda(ll, phr, pst)
+    if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1 or ll.shape != (N, tot):
+        raise _lib.GtosHipError("phrase_advance: ll must be an [N, tot] fp32 tensor with unit column stride")
+    assert phr.dim() == 3 and phr.shape[0] == B and phr.shape[1] <= PHRASE_MAX and phr.shape[2] <= PHRASE_LEN_MAX
+    assert phr.dtype == torch.int32 and phr.is_contiguous()
+    Cw, Lw = phr.shape[1], phr.shape[2]
+    assert Cw == 0 or Lw >= 1
+    assert pst.shape == (2, N) and pst.dtype == torch.int32 and pst.is_contiguous()
+    call("gtos_phrase_advance", B, k, Cw, Lw, t, V, tot, min_time_step, max_time_step, ptr(topv), ptr(topi), ptr(ll),
+         max(ll.stride(0), tot), ptr(phr) if Cw else None, ptr(flag_shared), ptr(flag_local), ptr(slot_score), ptr(beam_state),
+         ptr(bp_parent), ptr(bp_token), ptr(comp_step), ptr(comp_parent), ptr(comp_score), ptr(pst), ptr(active), stream())
+
+
 def coverage_step(t, k, align, pad, parent, cov_prev, cov_cur, cp, active):
     """The coverage of the graph nodes and its penalty at step t (gtos_coverage_step, the rule of csrc/coverage_kernels.h):
     cov_cur[s] = cov_prev[parent[s]] + align[s] (fp32 [N, n]; align: the alignment weights copy_log_likelihood consumes; parent int32

@@ -23,6 +23,9 @@ from the tokens the groups before it took at the same step.
 ``constraints`` turn either beam search into lexically constrained beam search with dynamic beam allocation (ConstrainedBeam; on the
 device csrc/constrain.hip, the rule in csrc/constrain_kernels.h): tokens every finished hypothesis of a graph must hold.
 
+``phrases`` do the same for constraints of several tokens (PhraseBeam; on the device csrc/phrase.hip, the rule in
+csrc/phrase_kernels.h): every finished hypothesis holds every phrase as consecutive tokens, a phrase listed twice twice.
+
 ``coverage`` turns either beam search into coverage-penalised beam search (CoverageBeam; on the device csrc/coverage.hip, the rule in
 csrc/coverage_kernels.h): every hypothesis accumulates the alignment weights of its steps over the graph nodes, and the selection
 prefers hypotheses that have looked at all of them.
@@ -210,6 +213,86 @@ class ConstrainedBeam(Beam):
         return [c[0] for c in kept]
 
 
+def phrase_step(phrases, met, open_, pos, token):
+    """The transition of csrc/phrase_kernels.h on one token: (met, open, pos) -> (met, open, pos).  A token that continues the open
+    phrase advances it and finishes it at its last token; any other token drops the progress and starts the lowest-index phrase whose
+    bit is clear and whose first token it is, if any.  No failure links."""
+    if open_ >= 0 and phrases[open_][pos] == token:
+        return (met | 1 << open_, -1, 0) if pos + 1 == len(phrases[open_]) else (met, open_, pos + 1)
+    for i, p in enumerate(phrases):
+        if not (met >> i) & 1 and p[0] == token:
+            return (met | 1 << i, -1, 0) if len(p) == 1 else (met, i, 1)
+    return met, -1, 0
+
+
+def phrase_state(seq, phrases):
+    """(met, open, pos) of ``seq`` (a list of token strings, e.g. Hypothesis.seq) under ``phrases`` (a list of non-empty token-string
+    lists): phrase_step over its tokens from (0, -1, 0).  met == (1 << len(phrases)) - 1: the sequence holds every phrase."""
+    state = (0, -1, 0)
+    for token in seq:
+        state = phrase_step(phrases, *state, token)
+    return state
+
+
+class PhraseBeam(Beam):
+    """Beam search of one sentence under phrase constraints: the rule of csrc/phrase_kernels.h in Python, ConstrainedBeam with
+    constraints of several tokens.  ``phrases``: non-empty lists of token strings every finished hypothesis must hold as consecutive
+    tokens, a phrase listed twice twice.  Live hypothesis h carries ``met[h]``, the bit mask of the phrases it has finished, and
+    ``progress[h]`` = (open, pos): the phrase in progress and its tokens matched so far, (-1, 0) when none is (phrase_step).  A step
+    pools, per live hypothesis in order, its top-k candidates -- an <END> only when every phrase is finished -- and then its forced
+    candidates: the next token of the open phrase or, with none open, the first token of every unfinished phrase in order (once per
+    token), each only when it is not among the top-k tokens and its log-likelihood is above -inf.  A candidate's bank is the number of
+    constraint tokens its next state holds: the lengths of the finished phrases plus pos.  Order, cut and placement as in
+    ConstrainedBeam.  With single-token phrases this is ConstrainedBeam, without phrases Beam."""
+
+    def __init__(self, beam_size, min_time_step, max_time_step, phrases):
+        super().__init__(beam_size, min_time_step, max_time_step)
+        self.phrases = [list(p) for p in phrases]
+        assert all(self.phrases), "a phrase holds at least one token"
+        self.met, self.progress = [0], [(-1, 0)]
+
+    def bank(self, met, open_, pos):
+        return sum(len(p) for i, p in enumerate(self.phrases) if (met >> i) & 1) + pos
+
+    def advance(self, last_steps, forced):
+        """last_steps as in Beam.advance; forced[h]: for live hypothesis h a dict from every token of the phrases to its log-likelihood
+        (as the selection sees it, after repeat-n-gram blocking); which of them enter the pool is decided here.  Returns the parents
+        like Beam.advance."""
+        full = (1 << len(self.phrases)) - 1
+        pool = []                                                       # (parent, token, score, next state), in pool position order
+        for parent, (steps, want) in enumerate(zip(last_steps, forced)):
+            base, met, (open_, pos) = self.hypotheses[parent].score, self.met[parent], self.progress[parent]
+            for token, ll in steps:
+                if token == END and met != full:
+                    continue
+                pool.append((parent, token, float('-inf') if token == UNK else base + ll, phrase_step(self.phrases, met, open_, pos, token)))
+            top = [token for token, _ in steps]
+            if open_ >= 0:
+                offers = [self.phrases[open_][pos]]
+            else:
+                offers = []
+                for i, p in enumerate(self.phrases):
+                    if not (met >> i) & 1 and p[0] not in offers:
+                        offers.append(p[0])
+            for token in offers:
+                if token in top or not want[token] > float('-inf'):
+                    continue
+                pool.append((parent, token, float('-inf') if token == UNK else base + want[token],
+                             phrase_step(self.phrases, met, open_, pos, token)))
+        banks = {}
+        for c in pool:
+            banks.setdefault(self.bank(*c[3]), []).append(c)
+        ranked = []
+        for bank, cands in banks.items():
+            cands.sort(key=lambda c: c[2], reverse=True)                # stable: ties keep pool order
+            ranked.extend((q, -bank, c) for q, c in enumerate(cands))
+        ranked.sort(key=lambda x: x[:2])                                # (q, bank) is unique
+        kept = self.place([c for _, _, c in ranked])
+        self.met = [c[3][0] for c in kept]
+        self.progress = [c[3][1:] for c in kept]
+        return [c[0] for c in kept]
+
+
 class CoveredHypothesis(Hypothesis):
     __slots__ = ("cp", "coverage")
 
@@ -275,7 +358,7 @@ def banned_tokens(y, n):
     return [y[i + n - 1] for i in range(t - n + 1) if y[i:i + n - 1] == suffix]
 
 
-def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage=None):
+def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage=None, phrases=None):
     """Runs all beams to completion.  ``model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, topk)`` ->
     (state, results); ``state`` is opaque here except that every tensor in it has the hypothesis axis at dim 1.  With
     ``no_repeat_ngram`` = n > 0 the call also gets, per hypothesis, the output ids that would repeat an n-gram of its tokens
@@ -288,7 +371,10 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
     ``coverage`` = beta (not with groups or constraints): coverage-penalised search -- every (fresh) beam is searched as a
     CoverageBeam and then holds that search's lists and steps; the decode call also returns the alignment weights, the live hypotheses'
     coverage is one device tensor gathered with the caches, ops.coverage_step (the kernel of the device search, a hypothesis its own
-    parent) adds and reduces it, and the host reads penalty and coverage in one copy per step."""
+    parent) adds and reduces it, and the host reads penalty and coverage in one copy per step.
+    ``phrases`` (one list of token-string lists per graph, not with groups, constraints or coverage): phrase-constrained search --
+    every (fresh) beam is searched as a PhraseBeam and then holds that search's lists, steps, ``met`` and ``progress``; ``want`` is per
+    hypothesis the output ids of the distinct tokens of its graph's phrases."""
     device = memory['probe'].device
     state = None
     result = beams
@@ -298,6 +384,12 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
         beams = [CoverageBeam(b.beam_size, b.min_time_step, b.max_time_step, coverage) for b in beams]
         live = lambda beam: beam.hypotheses
         ones = torch.ones(3, dtype=torch.int32, device=device)
+    elif phrases is not None:
+        assert groups == 1 and diversity == 0.0 and constraints is None and len(phrases) == len(beams), "phrases: one list per graph, no groups, no constraints"
+        beams = [PhraseBeam(b.beam_size, b.min_time_step, b.max_time_step, p) for b, p in zip(beams, phrases)]
+        phrase_tokens = [sorted(set(w for p in ps for w in p)) for ps in phrases]
+        cons_id = constraint_ids(model, memory['local_idx2token'], phrase_tokens)
+        live = lambda beam: beam.hypotheses
     elif constraints is not None:
         assert groups == 1 and diversity == 0.0 and len(constraints) == len(beams), "constraints: one list per graph, no groups"
         beams = [ConstrainedBeam(b.beam_size, b.min_time_step, b.max_time_step, c) for b, c in zip(beams, constraints)]
@@ -326,10 +418,13 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
         if not owners:
             break
         beam_of_hyp = torch.tensor(owners, dtype=torch.int64, device=device)
-        if constraints is not None:
+        if constraints is not None or phrases is not None:
             state, results, lls = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size,
                                                             banned if no_repeat_ngram else None, want=[cons_id[bi] for bi in owners])
-            forced = [list(zip(constraints[bi], row)) for bi, row in zip(owners, lls)]
+            if phrases is not None:
+                forced = [dict(zip(phrase_tokens[bi], row)) for bi, row in zip(owners, lls)]
+            else:
+                forced = [list(zip(constraints[bi], row)) for bi, row in zip(owners, lls)]
         elif coverage is not None:
             state, results, align = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size,
                                                               banned if no_repeat_ngram else None, want_align=True)
@@ -367,8 +462,11 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
         for beam, run in zip(result, beams):
             if coverage is not None:
                 beam.hypotheses, beam.completed_hypotheses, beam.steps = run.hypotheses, run.completed_hypotheses, run.steps
+            elif phrases is not None:
+                beam.hypotheses, beam.completed_hypotheses, beam.steps = run.hypotheses, run.completed_hypotheses, run.steps
+                beam.met, beam.progress = run.met, run.progress
             elif constraints is not None:
-                beam.hypotheses, beam.completed_hypotheses, beam.steps, beam.met = run.hypotheses, run.completed_hypotheses, run.steps, run.met
+                beam.hypotheses, beam.completed_hypotheses, beam.steps, beam.met =run.hypotheses, run.completed_hypotheses, run.steps, run.met
             else:
                 gather_groups(beam, run.groups)
     return result
@@ -510,7 +608,7 @@ def _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout
 
 
 def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0, groups=1, diversity=0.0, grouped=None,
-                       constraints=None, constrained=None, coverage=None, covered=None):
+                       constraints=None, constrained=None, coverage=None, covered=None, phrases=None, phrased=None):
     """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
     decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
     steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
@@ -529,13 +627,22 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat
     ``coverage`` = beta (not with groups or constraints): coverage-penalised search (the rule of csrc/coverage_kernels.h, CoverageBeam
     on the host) -- per step gtos_coverage_step before the plain top-k and gtos_coverage_advance as the advance, the plain reorder; a
     beam's hypotheses are then CoveredHypothesis objects.  ``covered`` = True takes that route even without a penalty (beta = 0: it
-    must give the plain search's beams, with the coverage reported)."""
+    must give the plain search's beams, with the coverage reported).
+    ``phrases`` (one list of token-string lists per graph, not with groups, constraints or coverage): phrase-constrained search (the
+    rule of csrc/phrase_kernels.h, PhraseBeam on the host) -- the plain tables plus the slots' packed states and the phrase ids, a step's
+    advance being gtos_phrase_advance between the plain top-k and the plain reorder; a beam then also carries ``met`` and ``progress``
+    of its live hypotheses.  ``phrased`` = True takes that route even without phrases (it must give the plain search's beams)."""
+    if phrased is None:
+        phrased = phrases is not None
     if grouped is None:
         grouped = groups != 1 or diversity != 0.0
     if constrained is None:
         constrained = constraints is not None
     if covered is None:
         covered = coverage is not None
+    if phrased:
+        assert not grouped and not constrained and not covered, "phrases do not combine with groups, constraints or coverage"
+        return _phrase_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, phrases)
     if covered:
         assert not grouped and not constrained, "coverage does not combine with groups or constraints"
         return _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, 0.0 if coverage is None else float(coverage))
@@ -598,6 +705,45 @@ def _constrained_search_device(model, memory, beams, sync_every, stats, no_repea
         return beams_
     return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill,
                        fresh=lambda beam: setattr(beam, 'met', [0]))
+
+
+def _phrase_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, phrases):
+    """The phrase route of beam_search_device: the plain launch sequence per step with gtos_phrase_advance as the advance (it reads ll
+    after the n-gram kernel, so a banned token is not forced) and the same host reads."""
+    if phrases is None:
+        phrases = [[] for _ in beams]
+    assert len(phrases) == len(beams), "phrases: one list per graph"
+
+    def layout(d):
+        ids = [constraint_ids(model, [local] * len(ps), ps) for local, ps in zip(d.local, phrases)]
+        Cw = max([len(x) for x in ids] + [0])
+        Lw = max([len(p) for x in ids for p in x] + [1])
+        if (Cw > ops.PHRASE_MAX or Lw > ops.PHRASE_LEN_MAX or any(not p for x in ids for p in x)
+                or any(sum(len(p) for p in x) > ops.PHRASE_TOKENS_MAX for x in ids) or any(not 0 <= i < d.tot for x in ids for p in x for i in p)):
+            raise ValueError("phrases: at most %d per graph, each of 1 to %d output ids of the batch, at most %d ids per graph"
+                             % (ops.PHRASE_MAX, ops.PHRASE_LEN_MAX, ops.PHRASE_TOKENS_MAX))
+        rows = [[p + [-1] * (Lw - len(p)) for p in x] + [[-1] * Lw] * (Cw - len(x)) for x in ids]
+        d.phr = torch.tensor(rows, dtype=torch.int32).view(d.B, Cw, Lw).to(memory['probe'].device)
+        return _plain_cuts(d, d.B, ints=[('pst', (2, d.N), 0)])
+
+    def step(d, t, ll, cur, nxt, tok_out, char_out):
+        topv, topi = ops.beam_topk(ll, d.k)
+        ops.phrase_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, topv, topi, ll, d.phr, *_plain_tables(d), d.arr['pst'], d.arr['active'])
+        _plain_reorder(d, t, cur, nxt, tok_out, char_out)
+
+    def fresh(beam):
+        beam.met, beam.progress = [0], [(-1, 0)]
+
+    def fill(beams_, k, pst, state, **tables):
+        fill_beams(beams_, k, state=state, **tables)
+        N = len(beams_) * k
+        for b, beam in enumerate(beams_):                    # the row the beam's last advance wrote: step t writes row (t + 1) % 2
+            steps, nlive = state[4 * b], state[4 * b + 2]
+            words = [pst[(steps % 2) * N + b * k + j] for j in range(nlive)] if steps else [0]
+            beam.met = [w & 0xFFFF for w in words]
+            beam.progress = [((w >> 16 & 31) - 1, w >> 21 & 31) for w in words]
+        return beams_
+    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill, fresh=fresh)
 
 
 def _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, beta):

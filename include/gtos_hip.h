@@ -573,6 +573,28 @@ int gtos_coverage_advance(int B, int k, int t, int V, int tot, int min_time_step
                           double* comp_score, const double* cp, const float* cov_cur, double* slot_cp, double* comp_cp,
                           float* comp_cov, float* slot_cov, int* active, void* stream);
 
+/* ---- Phrase-constrained beam search on the device (ABI 30; csrc/phrase.hip, the rule in csrc/phrase_kernels.h), driven by
+ * gtos_amd.search.beam_search_device(phrases=): gtos_constrain_advance with constraints of several tokens.  phr int32 [B, Cw, Lw]: row
+ * (b, i) the output ids of phrase i of graph b, of the plain class, then -1 (Cw <= 16 phrases of at most Lw <= 16 ids; an empty phrase
+ * ends the graph's list, as does a phrase with which the graph would hold more than 64 ids; a phrase listed twice must occur twice; phr
+ * may be null when Cw == 0).  pst int32 [2, N]: per slot the packed state -- bits 0-15 the mask of the phrases finished, bits 16-20 the
+ * phrase in progress plus one (0: none), bits 21-25 the tokens of it matched so far -- zero at the start; step t reads row t % 2 and
+ * writes row (t + 1) % 2.  The rule has no counterpart in generator/search.py.  The top-k pass is gtos_beam_topk(ll, k), the reorder
+ * gtos_beam_reorder: every other table is gtos_beam_advance's, in its format.
+ * _advance (one workgroup per graph, step t < max_time_step): gtos_constrain_advance with the state stepped token by token (a token
+ *   that continues the phrase in progress advances it, and finishes it at its last token; any other token drops the progress and starts
+ *   the lowest-index unfinished phrase that begins with it, if any: no failure links), the bank being the ids of the finished phrases
+ *   plus those matched of the one in progress, and the forced candidates being the next id of the phrase in progress or, with none in
+ *   progress, the first id of every unfinished phrase (once per id).  <END> is absent unless every phrase is finished.  With
+ *   one-id phrases of distinct ids the tables are gtos_constrain_advance's, without phrases gtos_beam_advance's.
+ *   SHAPES (-10 outside): 1 <= k <= 32, 0 <= Cw <= 16, 0 <= Lw <= 16 (>= 1 when Cw > 0), 0 <= t < max_time_step,
+ *   1 <= V <= tot <= ld; -23 for a null pointer (flag_local may be null when tot == V, phr when Cw == 0). */
+int gtos_phrase_advance(int B, int k, int Cw, int Lw, int t, int V, int tot, int min_time_step, int max_time_step,
+                        const float* topv, const int* topi, const float* ll, int64_t ld, const int* phr,
+                        const uint8_t* flag_shared, const uint8_t* flag_local, double* slot_score, int* beam_state,
+                        int* bp_parent, int* bp_token, int* comp_step, int* comp_parent, double* comp_score, int* pst,
+                        int* active, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
