@@ -167,6 +167,51 @@ def check_coverage(beta, search, groups, constraints):
     return float(beta)
 
 
+def check_avoid(avoid, constraints, phrases, local_idx2token, vocab):
+    """The argument checks of Generator.work(avoid=), for every search: None passes as None.  Otherwise ValueError unless ``avoid``
+    holds, per graph of ``local_idx2token`` (the batch's copy tables), a list of entries, an entry being a token string (one word) or
+    a non-empty list or tuple of token strings (a phrase), none of them <PAD>, <STR>, <END> or <UNK>.  An entry with a string the
+    graph cannot produce (neither one of its copy tokens nor a word of ``vocab``, the predictable-token vocabulary, with an id of its
+    own) can never occur and is dropped, as is an exact duplicate; what is left holds at most ops.AVOID_TOKENS_MAX tokens per graph.
+    Contradictions with the graph's ``constraints`` / ``phrases`` (as their checks return them, or None) are refused: a one-word
+    entry that is a constraint, and an entry that occurs as consecutive tokens of a phrase.  -> a list of lists of lists: per graph
+    the entries that apply, each a list of strings."""
+    if avoid is None:
+        return None
+    if isinstance(avoid, str) or not isinstance(avoid, (list, tuple)) or len(avoid) != len(local_idx2token):
+        raise ValueError("avoid holds one list of entries per graph: %d graphs, got %r"
+                         % (len(local_idx2token), avoid if not isinstance(avoid, (list, tuple)) else len(avoid)))
+    out = []
+    for b, (entries, local) in enumerate(zip(avoid, local_idx2token)):
+        if isinstance(entries, str) or not isinstance(entries, (list, tuple)):
+            raise ValueError("avoid[%d] is a list of words and phrases, got %r" % (b, entries))
+        copies = set(local.values())
+        kept = []
+        for entry in entries:
+            words = [entry] if isinstance(entry, str) else entry
+            if not isinstance(words, (list, tuple)) or not words:
+                raise ValueError("avoid[%d]: an entry is a token string or a non-empty list of token strings, got %r" % (b, entry))
+            for w in words:
+                if not isinstance(w, str):
+                    raise ValueError("avoid[%d]: an entry holds token strings, got %r" % (b, w))
+                if w in (PAD, STR, END, UNK):
+                    raise ValueError("avoid[%d]: %s cannot be avoided" % (b, w))
+            words = list(words)
+            if words in kept or any(w not in copies and vocab.token2idx(w) == vocab.unk_idx for w in words):
+                continue                                                # a duplicate, or an entry that can never occur
+            if len(words) == 1 and constraints is not None and words[0] in constraints[b]:
+                raise ValueError("avoid[%d]: %r is one of the graph's constraints" % (b, words[0]))
+            for phrase in phrases[b] if phrases is not None else ():
+                if any(list(phrase[i:i + len(words)]) == words for i in range(len(phrase) - len(words) + 1)):
+                    raise ValueError("avoid[%d]: %r occurs in the graph's phrase %r" % (b, words, list(phrase)))
+            kept.append(words)
+        if sum(len(words) for words in kept) > ops.AVOID_TOKENS_MAX:
+            raise ValueError("avoid[%d]: at most %d tokens per graph, got %d"
+                             % (b, ops.AVOID_TOKENS_MAX, sum(len(words) for words in kept)))
+        out.append(kept)
+    return out
+
+
 Coverage = collections.namedtuple("Coverage", "coverage cp tokens graph_of")
 Coverage.__doc__ = """What Generator.coverage returns, all DEVICE tensors over N sequences: coverage [N,n] fp32 (per graph node the
 alignment weight summed over the sequence's target positions, <END> included), cp [N] fp64 (the coverage penalty of that row: the sum
@@ -306,7 +351,8 @@ class Generator(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ inference
     def work(self, data, beam_size, max_time_step, min_time_step=1, search="host", *, temperature=1.0, top_k=0, top_p=1.0,
-             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage_penalty=None, phrases=None):
+             seed=None, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage_penalty=None, phrases=None,
+             avoid=None):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
         step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
@@ -335,7 +381,15 @@ class Generator(nn.Module):
         with constraints of several tokens (gtos_amd.search.PhraseBeam, the rule of csrc/phrase_kernels.h; on the device by
         gtos_phrase_advance).  A phrase listed twice must occur twice; the strings resolve as for ``constraints`` (check_phrases).  A
         returned beam then carries ``met``, the bit masks of the phrases its live hypotheses have finished, and ``progress``, per live
-        hypothesis (open, pos): the phrase in progress and its tokens matched so far, (-1, 0) when none is."""
+        hypothesis (open, pos): the phrase in progress and its tokens matched so far, (-1, 0) when none is.
+        ``avoid`` (any search, with every other option): negative constraints -- one list of entries per graph (a list may be empty),
+        an entry being a token string or a non-empty list of token strings that the output must NOT hold as consecutive tokens: a
+        continuation that would complete an entry is scored -inf before the selection, like a repeated n-gram (the rule of
+        csrc/avoid_kernels.h, a shift-and matcher word per hypothesis; on the device by gtos_avoid_block, on the host by
+        gtos_amd.search.avoided_tokens).  The strings resolve as for ``constraints``; an entry the graph cannot produce and a
+        duplicate are dropped, at most ops.AVOID_TOKENS_MAX tokens per graph remain, and an entry that one of the graph's
+        ``constraints`` or ``phrases`` demands is refused (check_avoid).  A returned beam then carries ``avoid``, the entries that
+        were applied, as lists of strings."""
         if search not in ("host", "device", "sample"):
             raise ValueError("search must be 'host', 'device' or 'sample', got %r" % (search,))
         no_repeat_ngram = check_no_repeat_ngram(no_repeat_ngram, search, max_time_step)
@@ -346,6 +400,8 @@ class Generator(nn.Module):
         if phrases is not None:
             phrases = check_phrases(phrases, search, groups, constraints, coverage_penalty, data['local_idx2token'],
                                     self.vocabs['predictable_token'])
+        if avoid is not None:
+            avoid = check_avoid(avoid, constraints, phrases, data['local_idx2token'], self.vocabs['predictable_token'])
         if search == "sample":
             check_sampling(beam_size, temperature, top_k, top_p, seed)
             if seed is None:
@@ -378,12 +434,17 @@ class Generator(nn.Module):
                 beams = [CoverageBeam(beam_size, min_time_step, max_time_step, coverage_penalty) for _ in beams]
             if phrases is not None:                                                        # None: likewise
                 block.update(phrases=phrases)
+            if avoid is not None and any(avoid):                                           # nothing to avoid: likewise
+                block.update(avoid=avoid)
             if search == "device":
                 beam_search_device(self, memory, beams, **block)
             elif search == "sample":
                 sample_device(self, memory, beams, temperature, top_k, top_p, seed, **block)
             else:
                 beam_search(self, beams, memory, **block)
+            if avoid is not None:
+                for beam, entries in zip(beams, avoid):
+                    beam.avoid = entries
         return beams
 
     # ------------------------------------------------------------------------------------------------ teacher-forced scoring

@@ -1579,3 +1579,33 @@ def ngram_block(t, k, n, ll, parent, token, hist_prev, hist_cur, active):
         assert x is None or x.is_contiguous()
     call("gtos_ngram_block", N, k, t, max_t, n, tot, ptr(ll), max(ll.stride(0), tot), ptr(parent), ptr(token), ptr(hist_prev),
          ptr(hist_cur), ptr(active), stream())
+
+
+# ---------------------------------------------------------------------------------------------- negative constraints
+# (csrc/avoid.hip; gtos_amd.search._slot_decode launches it for both device decoders)
+AVOID_TOKENS_MAX = 64    # MAX_POS of csrc/avoid_kernels.h: the pattern positions of a graph, one per lane of a wave
+
+
+def avoid_block(t, k, ll, parent, token, pat, init, last, n_pos, state_prev, state_cur, active):
+    """Before the selection of step t >= 0 (gtos_avoid_block): slot s's matcher word state_cur[s] = ((state_prev[parent[s]] << 1) |
+    init[b]) & MASK(token[s]) (int64 [N] each, read as 64 bits; parent / token int32 [N], what every slot took at step t - 1; parent
+    None: a slot is its own parent; t == 0: neither is read, every word becomes 0) under the tables of its graph b = s // k (pat int32
+    [B, 64], init / last int64 [B], n_pos int32 [B]; search.avoid_tables), and the columns of ll [N, tot] fp32 that would complete an
+    avoid entry set to -inf, in place.  At t >= 1 slots with a negative parent or token are left alone."""
+    require_cuda(ll, parent, token, pat, init, last, n_pos, state_prev, state_cur, active)
+    if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1:
+        raise _lib.GtosHipError("avoid_block: ll must be a 2-D fp32 tensor with unit column stride")
+    N, tot = ll.shape
+    assert k >= 1 and N % k == 0
+    B = N // k
+    assert pat.shape == (B, AVOID_TOKENS_MAX) and pat.dtype == torch.int32 and n_pos.dtype == torch.int32 and n_pos.numel() == B
+    assert init.dtype == torch.int64 and init.numel() == B and last.dtype == torch.int64 and last.numel() == B
+    assert state_prev.dtype == torch.int64 and state_prev.numel() == N and state_cur.dtype == torch.int64 and state_cur.numel() == N
+    assert state_prev.data_ptr() != state_cur.data_ptr(), "avoid_block: the two state buffers alternate"
+    assert t == 0 or (token is not None and token.dtype == torch.int32 and token.numel() == N)
+    assert t == 0 or parent is None or (parent.dtype == torch.int32 and parent.numel() == N)
+    assert active.numel() == 3 and active.dtype == torch.int32
+    for x in (pat, init, last, n_pos, state_prev, state_cur, active) + ((parent, token) if t else ()):
+        assert x is None or x.is_contiguous()
+    call("gtos_avoid_block", N, k, t, tot, ptr(ll), max(ll.stride(0), tot), ptr(parent) if t else None, ptr(token) if t else None,
+         ptr(pat), ptr(init), ptr(last), ptr(n_pos), ptr(state_prev), ptr(state_cur), ptr(active), stream())

@@ -30,6 +30,9 @@ csrc/phrase_kernels.h): every finished hypothesis holds every phrase as consecut
 csrc/coverage_kernels.h): every hypothesis accumulates the alignment weights of its steps over the graph nodes, and the selection
 prefers hypotheses that have looked at all of them.
 
+``avoid`` gives every search negative constraints (avoided_tokens; on the device csrc/avoid.hip, the rule in csrc/avoid_kernels.h):
+words and phrases the output of a graph must not hold, banned in ll before the selection like a repeated n-gram.
+
 ``sample_device`` decodes by sampling instead (csrc/sample.hip): the same fixed slots, one independent sample per slot with
 temperature / top-k / top-p, and Beam objects filled the same way.
 """
@@ -358,7 +361,47 @@ def banned_tokens(y, n):
     return [y[i + n - 1] for i in range(t - n + 1) if y[i:i + n - 1] == suffix]
 
 
-def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage=None, phrases=None):
+def avoided_tokens(seq, entries):
+    """The rule of csrc/avoid_kernels.h on Python lists: the last token of every entry of ``entries`` (non-empty token lists) whose
+    other tokens ``seq`` ends in -- the tokens that would complete an avoid entry -- in entry order, repeats included."""
+    seq = list(seq)
+    t = len(seq)
+    return [p[-1] for p in (list(p) for p in entries) if len(p) - 1 <= t and seq[t - len(p) + 1:] == p[:-1]]
+
+
+def avoid_tables(ids):
+    """The per-graph tables of gtos_avoid_block from the per-graph lists of avoid entries (non-empty lists of output ids): (pat, one
+    row of ops.AVOID_TOKENS_MAX ids per graph, the entries concatenated, then -1; init; last; n_pos), init / last the bit masks of the
+    entries' first / last positions as signed 64-bit integers.  ValueError for an empty entry or more positions than a row holds."""
+    W = ops.AVOID_TOKENS_MAX
+    signed = lambda x: x - (1 << 64) if x >> 63 else x
+    pat, init, last, n_pos = [], [], [], []
+    for b, entries in enumerate(ids):
+        row, first, end = [], 0, 0
+        for p in entries:
+            if not len(p) or len(row) + len(p) > W:
+                raise ValueError("avoid: graph %d holds an empty entry or more than %d ids" % (b, W))
+            first |= 1 << len(row)
+            row.extend(int(i) for i in p)
+            end |= 1 << len(row) - 1
+        pat.append(row + [-1] * (W - len(row)))
+        init.append(signed(first))
+        last.append(signed(end))
+        n_pos.append(len(row))
+    return pat, init, last, n_pos
+
+
+def avoid_ids(model, local_idx2token, avoid):
+    """Per graph the avoid entries (lists of token strings) as lists of output ids by constraint_ids' convention; None when ``avoid``
+    is None or every graph's list is empty: nothing to avoid."""
+    if avoid is None or not any(avoid):
+        return None
+    assert len(avoid) == len(local_idx2token), "avoid: one list per graph"
+    return [constraint_ids(model, [local] * len(entries), entries) for local, entries in zip(local_idx2token, avoid)]
+
+
+def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage=None, phrases=None,
+                avoid=None):
     """Runs all beams to completion.  ``model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, topk)`` ->
     (state, results); ``state`` is opaque here except that every tensor in it has the hypothesis axis at dim 1.  With
     ``no_repeat_ngram`` = n > 0 the call also gets, per hypothesis, the output ids that would repeat an n-gram of its tokens
@@ -374,8 +417,15 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
     parent) adds and reduces it, and the host reads penalty and coverage in one copy per step.
     ``phrases`` (one list of token-string lists per graph, not with groups, constraints or coverage): phrase-constrained search --
     every (fresh) beam is searched as a PhraseBeam and then holds that search's lists, steps, ``met`` and ``progress``; ``want`` is per
-    hypothesis the output ids of the distinct tokens of its graph's phrases."""
+    hypothesis the output ids of the distinct tokens of its graph's phrases.
+    ``avoid`` (one list of entries per graph, an entry a non-empty list of token strings; with every other option): negative
+    constraints -- per hypothesis the output ids that would complete an entry of its graph (avoided_tokens on the strings after
+    <STR>) join the banned ids.  None, or every list empty: nothing of it."""
     device = memory['probe'].device
+    if avoid is not None and not any(avoid):
+        avoid = None
+    assert avoid is None or len(avoid) == len(beams), "avoid: one list per graph"
+    use_banned = bool(no_repeat_ngram) or avoid is not None
     state = None
     result = beams
     cov = None
@@ -400,7 +450,7 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
         live = GroupBeam.live_hypotheses
     else:
         live = lambda beam: beam.hypotheses
-    if no_repeat_ngram:
+    if use_banned:
         pv = model.vocabs['predictable_token']
         copy_id = [{w: i for i, w in local.items()} for local in memory['local_idx2token']]
     while True:
@@ -412,28 +462,30 @@ def beam_search(model, beams, memory, no_repeat_ngram=0, groups=1, diversity=0.0
                     owners.append(bi)
                     tokens.append(hyp.seq[-1])
                     offset = len(hyp.seq) - 1
-                    if no_repeat_ngram:
-                        banned.append([copy_id[bi][w] if w in copy_id[bi] else pv.token2idx(w)
-                                       for w in banned_tokens(hyp.seq[1:], no_repeat_ngram)])
+                    if use_banned:
+                        words = banned_tokens(hyp.seq[1:], no_repeat_ngram) if no_repeat_ngram else []
+                        if avoid is not None:
+                            words = words + avoided_tokens(hyp.seq[1:], avoid[bi])
+                        banned.append([copy_id[bi][w] if w in copy_id[bi] else pv.token2idx(w) for w in words])
         if not owners:
             break
         beam_of_hyp = torch.tensor(owners, dtype=torch.int64, device=device)
         if constraints is not None or phrases is not None:
             state, results, lls = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size,
-                                                            banned if no_repeat_ngram else None, want=[cons_id[bi] for bi in owners])
+                                                            banned if use_banned else None, want=[cons_id[bi] for bi in owners])
             if phrases is not None:
                 forced = [dict(zip(phrase_tokens[bi], row)) for bi, row in zip(owners, lls)]
             else:
                 forced = [list(zip(constraints[bi], row)) for bi, row in zip(owners, lls)]
         elif coverage is not None:
             state, results, align = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size,
-                                                              banned if no_repeat_ngram else None, want_align=True)
+                                                              banned if use_banned else None, want_align=True)
             pad = memory['graph_padding_mask'].index_select(1, beam_of_hyp).contiguous()
             prev, cov = torch.zeros_like(align) if cov is None else cov, torch.empty_like(align)
             cp = torch.empty(len(owners), dtype=torch.float64, device=device)
             ops.coverage_step(offset, 1, align, pad, None, prev, cov, cp, ones)
             rows = torch.cat([cp.unsqueeze(1), cov.masked_fill(pad.t(), 0.).double()], 1).tolist()       # the step's one extra read
-        elif no_repeat_ngram:
+        elif use_banned:
             state, results = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size, banned)
         else:
             state, results = model.decode_step_batched(tokens, state, memory, beam_of_hyp, offset, beams[0].beam_size)
@@ -490,7 +542,7 @@ def _arena(dtype, cuts, dev):
 
 
 def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, layout, step, fill, no_repeat_ngram=0, taken=None,
-                 want_align=False, extra_reads=0):
+                 want_align=False, extra_reads=0, avoid=None):
     """The fixed-slot decode loop (the contract of csrc/slot_kernels.h) behind ``who``, a public function: B graphs x k slots, N = B*k,
     slot s belongs to graph s // k, the graph memory gathered per slot once, every slot decoded every step (a dead slot on the
     padding input), the input of step t + 1 written by step t's kernels into the other of two buffers.  The loop reads the device's
@@ -508,7 +560,11 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
         ``no_repeat_ngram`` = n > 0, the rule of csrc/ngram_kernels.h: two int32 [N, max_t] history buffers alternate by step parity and
         ops.ngram_block bans, in ll, the columns that would repeat an n-gram, at every step t >= 1 before step().  n = 0: nothing of it.
       want_align: the decoder also returns the slots' alignment weights [N, n] fp32, which step() finds as d.align;
-      extra_reads: host reads fill() makes beyond the two arenas, counted in stats['host_reads']."""
+      extra_reads: host reads fill() makes beyond the two arenas, counted in stats['host_reads'];
+      avoid: per graph a list of avoid entries (non-empty lists of output ids, avoid_ids), the rule of csrc/avoid_kernels.h: the
+        per-graph tables (avoid_tables) are built once, two int64 [N] matcher-state buffers alternate by step parity and
+        ops.avoid_block bans, in ll, the columns that would complete an entry, at every step t >= 0 before step() (with taken(d, t - 1)
+        for t >= 1).  None, or every list empty: nothing of it."""
     B = len(beams)
     if not B:
         return beams
@@ -542,6 +598,14 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
     tok[0].view(B, k // width, width)[:, :, :live0] = tab['start_tok']
     chars[0].view(B, k // width, width, C)[:, :, :live0] = tab['start_char']
     hist = [torch.zeros((N, max_t), dtype=torch.int32, device=dev) for _ in range(2)] if no_repeat_ngram else None
+    avo = None
+    if avoid is not None and any(avoid):
+        if len(avoid) != B or any(not 0 <= i < tot for entries in avoid for p in entries for i in p):
+            raise ValueError("avoid: one list of entries per graph, each id an output id of the batch")
+        pat, init, last, n_pos = avoid_tables(avoid)
+        avo = types.SimpleNamespace(pat=torch.tensor(pat, dtype=torch.int32).to(dev), init=torch.tensor(init, dtype=torch.int64).to(dev),
+                                    last=torch.tensor(last, dtype=torch.int64).to(dev), n_pos=torch.tensor(n_pos, dtype=torch.int32).to(dev),
+                                    state=[torch.zeros(N, dtype=torch.int64, device=dev) for _ in range(2)])
     for t in range(max_t):
         cur, nxt = t % 2, (t + 1) % 2
         if want_align:
@@ -551,6 +615,9 @@ def _slot_decode(who, model, memory, beams, sync_every, stats, copies, live0, la
         if no_repeat_ngram and t:
             parent, token = taken(d, t - 1)
             ops.ngram_block(t, k, no_repeat_ngram, ll, parent, token, hist[nxt], hist[cur], ints['active'])
+        if avo is not None:
+            parent, token = taken(d, t - 1) if t else (None, None)
+            ops.avoid_block(t, k, ll, parent, token, avo.pat, avo.init, avo.last, avo.n_pos, avo.state[nxt], avo.state[cur], ints['active'])
         step(d, t, ll, caches[cur % copies], caches[nxt % copies], tok[nxt][0], chars[nxt][0])
         n_steps += 1
         if (t + 1) % sync_every == 0 and t + 1 < max_t:
@@ -608,7 +675,7 @@ def _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout
 
 
 def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat_ngram=0, groups=1, diversity=0.0, grouped=None,
-                       constraints=None, constrained=None, coverage=None, covered=None, phrases=None, phrased=None):
+                       constraints=None, constrained=None, coverage=None, covered=None, phrases=None, phrased=None, avoid=None):
     """beam_search with selection, bookkeeping and state reorder on the device.  ``model``: a Generator (search_tables, slot_caches,
     decode_slots); ``memory``: per graph, as Generator.work builds it; ``beams``: fresh Beam objects of one (beam size, min, max
     steps), one per graph.  Slot s of the N = B*k slots belongs to graph s // k; at step 0 only slot 0 of each beam is live; dead slots
@@ -631,7 +698,11 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat
     ``phrases`` (one list of token-string lists per graph, not with groups, constraints or coverage): phrase-constrained search (the
     rule of csrc/phrase_kernels.h, PhraseBeam on the host) -- the plain tables plus the slots' packed states and the phrase ids, a step's
     advance being gtos_phrase_advance between the plain top-k and the plain reorder; a beam then also carries ``met`` and ``progress``
-    of its live hypotheses.  ``phrased`` = True takes that route even without phrases (it must give the plain search's beams)."""
+    of its live hypotheses.  ``phrased`` = True takes that route even without phrases (it must give the plain search's beams).
+    ``avoid`` (one list of entries per graph, an entry a non-empty list of token strings; with every route): negative constraints (the
+    rule of csrc/avoid_kernels.h, avoided_tokens on the host) -- one gtos_avoid_block per step in front of the route's selection, as
+    _slot_decode describes; None, or every list empty: the route's calls as they are without."""
+    avoid = avoid_ids(model, memory['local_idx2token'], avoid)
     if phrased is None:
         phrased = phrases is not None
     if grouped is None:
@@ -642,24 +713,24 @@ def beam_search_device(model, memory, beams, sync_every=8, stats=None, no_repeat
         covered = coverage is not None
     if phrased:
         assert not grouped and not constrained and not covered, "phrases do not combine with groups, constraints or coverage"
-        return _phrase_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, phrases)
+        return _phrase_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, phrases, avoid)
     if covered:
         assert not grouped and not constrained, "coverage does not combine with groups or constraints"
-        return _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, 0.0 if coverage is None else float(coverage))
+        return _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, 0.0 if coverage is None else float(coverage), avoid)
     if constrained:
         assert not grouped, "constraints do not combine with groups"
-        return _constrained_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, constraints)
+        return _constrained_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, constraints, avoid)
     if grouped:
-        return _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, groups, float(diversity))
+        return _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, groups, float(diversity), avoid)
 
     def step(d, t, ll, cur, nxt, tok_out, char_out):
         topv, topi = ops.beam_topk(ll, d.k)
         ops.beam_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, topv, topi, *_plain_tables(d), d.arr['active'])
         _plain_reorder(d, t, cur, nxt, tok_out, char_out)
-    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, lambda d: _plain_cuts(d, d.B), step, fill_beams)
+    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, lambda d: _plain_cuts(d, d.B), step, fill_beams, avoid=avoid)
 
 
-def _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, G, diversity):
+def _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, G, diversity, avoid=None):
     """The grouped route of beam_search_device: the same launch sequence per step (one top-k over the whole k, one advance, one
     reorder, the n-gram kernel when asked -- parents are global slot indices, so it works as it is) and the same host reads."""
     if beams:
@@ -673,10 +744,10 @@ def _group_search_device(model, memory, beams, sync_every, stats, no_repeat_ngra
     fill = lambda beams_, k, **tables: fill_beams(beams_, k, groups=G, **tables)
     fresh = lambda beam: gather_groups(beam, [Beam(g, beam.min_time_step, beam.max_time_step) for _ in range(G)])
     return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, lambda d: _plain_cuts(d, d.B * G), step, fill,
-                       live0=(g, 1) if beams else 1, fresh=fresh)
+                       live0=(g, 1) if beams else 1, fresh=fresh, avoid=avoid)
 
 
-def _constrained_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, constraints):
+def _constrained_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, constraints, avoid=None):
     """The constrained route of beam_search_device: the plain launch sequence per step with gtos_constrain_advance as the advance (it
     reads ll after the n-gram kernel, so a banned constraint is not forced) and the same host reads."""
     if constraints is None:
@@ -704,10 +775,10 @@ def _constrained_search_device(model, memory, beams, sync_every, stats, no_repea
             beam.met = [met[(steps % 2) * N + b * k + j] for j in range(nlive)] if steps else [0]
         return beams_
     return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill,
-                       fresh=lambda beam: setattr(beam, 'met', [0]))
+                       fresh=lambda beam: setattr(beam, 'met', [0]), avoid=avoid)
 
 
-def _phrase_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, phrases):
+def _phrase_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, phrases, avoid=None):
     """The phrase route of beam_search_device: the plain launch sequence per step with gtos_phrase_advance as the advance (it reads ll
     after the n-gram kernel, so a banned token is not forced) and the same host reads."""
     if phrases is None:
@@ -743,10 +814,10 @@ def _phrase_search_device(model, memory, beams, sync_every, stats, no_repeat_ngr
             beam.met = [w & 0xFFFF for w in words]
             beam.progress = [((w >> 16 & 31) - 1, w >> 21 & 31) for w in words]
         return beams_
-    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill, fresh=fresh)
+    return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill, fresh=fresh, avoid=avoid)
 
 
-def _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, beta):
+def _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ngram, beta, avoid=None):
     """The coverage route of beam_search_device.  Per step: the decoder (which also hands out its alignment weights),
     gtos_ngram_block if asked, gtos_coverage_step (coverage and penalty of every slot, two [N, n] buffers alternating by step parity as
     the n-gram histories do), gtos_beam_topk, gtos_coverage_advance, gtos_beam_reorder.  The fp64 arena also holds slot_cp / comp_cp;
@@ -786,7 +857,7 @@ def _covered_search_device(model, memory, beams, sync_every, stats, no_repeat_ng
             beam.hypotheses = [CoveredHypothesis(h.seq, h.score, slot_cp[b * k + j], rows[b * k + j]) for j, h in enumerate(beam.hypotheses)]
         return beams_
     return _beam_route(model, memory, beams, sync_every, stats, no_repeat_ngram, layout, step, fill, want_align=True, extra_reads=1,
-                       fresh=lambda beam: setattr(beam, 'hypotheses', [CoveredHypothesis([STR], 0., 0., [])]))
+                       fresh=lambda beam: setattr(beam, 'hypotheses', [CoveredHypothesis([STR], 0., 0., [])]), avoid=avoid)
 
 
 def slot_memory(memory, B, k):
@@ -848,12 +919,13 @@ def sample_bits(seed, graph, sample, t, cols):
     return SplitMix64(key).u64(int(cols.max()) + 1 if cols.size else 0)[cols]
 
 
-def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_every=8, stats=None, no_repeat_ngram=0):
+def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_every=8, stats=None, no_repeat_ngram=0, avoid=None):
     """Sampling decode on the device (csrc/sample.hip), the counterpart of beam_search_device with the same ``memory``: every graph
     gets ``beam_size`` independent samples in fixed slots (slot s is sample s % k of graph s // k), each drawing its next token by the
     rule of csrc/sample_kernels.h (temperature, top_k, top_p; <UNK>, other graphs' copy ids and <END> before min_time_step are never
     drawn) from a counter hash of (seed, graph, sample, step, column).  A sample never changes parent, so each layer keeps ONE
-    [max_time_step, N, 2d] cache and nothing is reordered; ``sync_every``, ``stats`` and ``no_repeat_ngram`` as in _slot_decode.  Returns the beams filled
+    [max_time_step, N, 2d] cache and nothing is reordered; ``sync_every``, ``stats`` and ``no_repeat_ngram`` as in _slot_decode, ``avoid`` as in
+    beam_search_device.  Returns the beams filled
     like a beam search's: completed_hypotheses (ended by <END>) by completion step, then sample index; hypotheses (unfinished) in
     sample order; score = the fp64 sum of the model's ll of the drawn tokens."""
     def layout(d):
@@ -866,7 +938,7 @@ def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_ev
                         d.owned, a['score'], a['state'], a['tokens'], a['active'], tab['tok_shared'], tab['tok_local'],
                         tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
     return _slot_decode("sample_device", model, memory, beams, sync_every, stats, 1, None, layout, step, fill_samples, no_repeat_ngram,
-                        lambda d, t: (None, d.arr['tokens'][t]))
+                        lambda d, t: (None, d.arr['tokens'][t]), avoid=avoid_ids(model, memory['local_idx2token'], avoid))
 
 
 def fill_samples(beams, k, state, tokens, score, token_string):

@@ -595,6 +595,28 @@ int gtos_phrase_advance(int B, int k, int Cw, int Lw, int t, int V, int tot, int
                         int* bp_parent, int* bp_token, int* comp_step, int* comp_parent, double* comp_score, int* pst,
                         int* active, void* stream);
 
+/* ---- Negative constraints of the device-resident decoders (ABI 31; csrc/avoid.hip, the rule in csrc/avoid_kernels.h), driven by
+ * gtos_amd.search._slot_decode for both of them: words and phrases the output of a graph must not hold (the negative constraints of
+ * Post & Vilar 2018 / Hu et al. 2019).  Graph b's entries, each a non-empty sequence of output ids, are concatenated into pat int32
+ * [B, 64] (row b: n_pos[b] <= 64 ids, then anything); init / last uint64 [B] have a bit at the first / last position of every entry.
+ * A slot carries one uint64 word D of the multi-pattern shift-and matcher: bit i set iff its output ends in the entry of position i
+ * up to position i.  A slot in state D may not take pat[i] for any bit i of ((D << 1) | init) & last: that column of its ll row
+ * becomes -inf.  The rule has no counterpart in generator/search.py; it is stated in full in csrc/avoid_kernels.h.
+ * _block (one wave per slot, four slots per workgroup) is launched once per step t >= 0, after the decoder's ll [N, tot] fp32 (row
+ *   stride ld >= tot) and before the step's selection; its order relative to gtos_ngram_block does not matter.  parent / token int32
+ *   [N]: what every slot took at step t - 1 (row t - 1 of bp_parent / bp_token; for the sampler parent = NULL, a slot is its own
+ *   parent, and row t - 1 of tokens); neither is read at t == 0, where every slot starts from D = 0 and only the one-id entries ban.
+ *   At t >= 1 a slot with parent < 0 (or >= N) or token < 0 is dead: its ll row and its state word are left as they are; a live slot s
+ *   gets state_cur[s] = ((state_prev[parent] << 1) | init) & MASK(token[s]), MASK(w) having bit i set iff pat[i] == w (uint64 [N]
+ *   each; the caller alternates the two buffers by step parity), then the bans of that word in ll[s, :], written in place; ids outside
+ *   [0, tot) ban nothing and every other element of ll stays as it is.  active int32 [3] as in csrc/slot_kernels.h, read only: a
+ *   step that does not run writes nothing.
+ *   SHAPES (-10 outside): t >= 0, tot >= 1, ld >= tot, k >= 1, N % k == 0, state_prev != state_cur; -23 for a null pointer other
+ *   than parent (and token at t == 0). */
+int gtos_avoid_block(int N, int k, int t, int tot, float* ll, int64_t ld, const int* parent, const int* token, const int* pat,
+                     const uint64_t* init, const uint64_t* last, const int* n_pos, const uint64_t* state_prev,
+                     uint64_t* state_cur, const int* active, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
