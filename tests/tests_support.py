@@ -51,7 +51,8 @@ def full_model_pair(dev, cfg_name, B, layers=None):
 # store one row or column too many is found whatever it wrote.  The default bands hold a full 256x256 macro tile of rows past the end:
 # a ragged tile that stores rows it should not lands inside the band, never past the allocation.
 NAN_BITS = {torch.float32: 0x7FC0A5A5, torch.bfloat16: 0x7FC5}
-_INT_OF = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float64: torch.int64}
+_INT_OF = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float64: torch.int64, torch.uint8: torch.uint8,
+           torch.int64: torch.int64}
 
 
 def _bits(t):
@@ -261,3 +262,67 @@ def bias_sum_bound(d4_stored, rows):
     """(fp64 column sums of the stored d4 rows, c_acc(rows) * column sums of |d4|)"""
     d = d4_stored.double()
     return d.sum(0), c_acc(rows) * d.abs().sum(0)
+
+
+# ------------------------------------------------------------------------------------------------ row kernels: fp64 and bounds
+# The gather / scatter / elementwise row kernels (csrc/tokenenc.hip, the middle of csrc/rowops.hip) against float64, with the same three
+# constants.  Where a kernel only moves or selects stored values the tests ask for equality; the functions below are for the rest.
+def c_acc_of(count):
+    """c_acc of a tensor of term counts (a count of 0 or 1 is one rounding)"""
+    return 4.0 * EPS32 * count.double().clamp(min=1.0).sqrt()
+
+
+def highway_bounds(y, x, dout, dtype):
+    """The highway gate of csrc/tokenenc.hip.  ``y`` [N, 2D] = (new_x | gate), ``x``, ``dout`` [N, D] as stored.  The sigmoid's error
+    c_fast(gate) reaches every output times the magnitude it multiplies; the fp32 products and sums add c_acc(1) of the terms (8 eps
+    for the four-factor product of dg).  relu and its gate are exact: dnx is 0 with no error wherever new_x <= 0.
+    Returns {name: (ref, bound)} for out, dnx, dg, dx."""
+    D = x.shape[1]
+    nx, g, x, go = y[:, :D].double(), y[:, D:].double(), x.double(), dout.double()
+    s, r, cf = torch.sigmoid(g), nx.clamp(min=0.0), c_fast(g)
+    on = (nx > 0).double()
+    ref = dict(out=s * x + (1 - s) * r, dnx=on * go * (1 - s), dg=go * (x - r) * s * (1 - s), dx=go * s)
+    u = dict(out=cf * (x - r).abs() + c_acc(1) * ((s * x).abs() + ((1 - s) * r).abs()),
+             dnx=on * (cf * go.abs() + c_acc(1) * ref["dnx"].abs()),
+             dg=cf * (go * (x - r)).abs() + 8 * EPS32 * ref["dg"].abs(),
+             dx=cf * go.abs() + c_acc(1) * ref["dx"].abs())
+    return {k: (ref[k], stored_bound(ref[k], u[k], dtype)) for k in ref}
+
+
+def dropped_rows_bounds(val, keep, p, dtype):
+    """Rows of stored values ``val`` (float64) through dropout: kept elements val / (1 - p) in fp32 (the quotient and the product:
+    c_acc(1) of the result) rounded to ``dtype``, dropped elements exactly 0 (bound 0).  p == 0: one rounding of val."""
+    ref = val * keep.double() * drop_scale(p) if p > 0 else val
+    return ref, stored_bound(ref, c_acc(1) * ref.abs() if p > 0 else torch.zeros_like(ref), dtype)
+
+
+def scatter_bounds(pre, tok, v):
+    """table[tok[n], :] += v[n, :] on top of the preload ``pre`` (fp32 atomics in any order).  ``v`` float64 [n, C].  Returns (ref, bound,
+    count): per element c_acc(count) * S with count the rows that share the token and S = |pre| + sum |v|.  A row with count 0 has to
+    stay bitwise what it was: the callers check that apart."""
+    tok = tok.long()
+    ref = pre.double().index_add(0, tok, v)
+    S = pre.double().abs().index_add(0, tok, v.abs())
+    count = torch.bincount(tok, minlength=pre.shape[0])
+    return ref, c_acc_of(count)[:, None] * S, count
+
+
+def gather_mean_bounds(bank, idx, dtype):
+    """out[p] = mean over the live (non-zero) entries of idx[p] of bank rows, row 0 never read.  Bound: c_acc(K) * S / cnt (the sum, the
+    reciprocal and the product) plus the stored rounding."""
+    b = bank.double().clone()
+    b[0] = 0.0
+    live = (idx != 0)
+    rows = b[idx.long()] * live.double()[..., None]
+    cnt = live.sum(1).clamp(min=1).double()[:, None]
+    ref = rows.sum(1) / cnt
+    return ref, stored_bound(ref, c_acc(idx.shape[1]) * rows.abs().sum(1) / cnt, dtype)
+
+
+def segment_sum_bounds(v, node_of_row, n_nodes, dtype=torch.bfloat16):
+    """dst[node] = sum of the node's rows ``v`` (float64 [rows, W]), fp32 accumulation in any order, one rounding to ``dtype``:
+    c_acc(cnt) * S per element with cnt the NODE's row count, so a two-row node is held to its own error.  Empty nodes: exactly 0."""
+    ref = torch.zeros(n_nodes, v.shape[1], dtype=torch.float64, device=v.device).index_add(0, node_of_row, v)
+    S = torch.zeros_like(ref).index_add(0, node_of_row, v.abs())
+    cnt = torch.bincount(node_of_row, minlength=n_nodes)
+    return ref, stored_bound(ref, c_acc_of(cnt)[:, None] * S, dtype)
