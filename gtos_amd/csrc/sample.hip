@@ -32,32 +32,6 @@ __device__ __forceinline__ bool col_allowed(const SampleArgs& a, int b, int c, f
     return allowed(a.flag_shared, a.flag_local, a.owned_local, a.V, a.tot, b, c, a.t, a.min_t, y);
 }
 
-// Block-wide reductions: every thread gets the result.  red: NW-entry LDS scratch, free again on return.
-__device__ double block_sum(double x, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
-
-__device__ void block_minmax(float& mx, float& mn, float* rmx, float* rmn) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, o));
-        mn = fminf(mn, __shfl_xor(mn, o));
-    }
-    if ((threadIdx.x & 63) == 0) { rmx[threadIdx.x >> 6] = mx; rmn[threadIdx.x >> 6] = mn; }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < NW; ++w) { mx = fmaxf(mx, rmx[w]); mn = fminf(mn, rmn[w]); }
-    __syncthreads();
-}
-
 // arg-max of (key, column) by wins(); the winner's column goes to every thread
 __device__ int block_argmax(double bk, int bc, double* rk, int* rc) {
 #pragma unroll

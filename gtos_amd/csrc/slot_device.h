@@ -1,5 +1,6 @@
 // Device half of the fixed-slot decode contract (csrc/slot_kernels.h), for the .hip files only: the register top-k pass over one
-// ll row and the write of a slot's next input, with the host-side helpers of their entry points.
+// ll row, the block reductions of the row kernels (csrc/sample.hip, csrc/sbs.hip) and the write of a slot's next input, with the
+// host-side helpers of their entry points.
 #pragma once
 #include "common.h"
 #include "slot_kernels.h"
@@ -66,6 +67,32 @@ __device__ void row_topk(const float* x, int tot, int k, Allowed allowed, float*
         for (int q = 0; q < n; ++q) rank += before(sv[q / k][q % k], si[q / k][q % k], a, ai);
         if (rank < k && ai != INT_MAX) { lv[rank] = a; lc[rank] = ai; }
     }
+    __syncthreads();
+}
+
+// Block-wide reductions: every thread gets the result.  red: NW-entry LDS scratch, free again on return.
+__device__ inline double block_sum(double x, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) s += red[w];
+    __syncthreads();
+    return s;
+}
+
+__device__ inline void block_minmax(float& mx, float& mn, float* rmx, float* rmn) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, o));
+        mn = fminf(mn, __shfl_xor(mn, o));
+    }
+    if ((threadIdx.x & 63) == 0) { rmx[threadIdx.x >> 6] = mx; rmn[threadIdx.x >> 6] = mn; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { mx = fmaxf(mx, rmx[w]); mn = fminf(mn, rmn[w]); }
     __syncthreads();
 }
 

@@ -22,7 +22,7 @@ from .encoder import TokenEncoder, RelationEncoder
 from .decoder import DecodeLayer
 from .transformer import Transformer, SinusoidalPositionalEmbedding, SelfAttentionMask
 from .graph_transformer import GraphTransformer, set_compute_dtype
-from .search import Beam, CoverageBeam, beam_search, beam_search_device, sample_device
+from .search import Beam, CoverageBeam, beam_search, beam_search_device, sample_device, stochastic_beam_search_device
 from .vocab import PAD, UNK, STR, END, lists_to_tensor, strings_to_char_tensor
 
 
@@ -39,6 +39,15 @@ def check_sampling(samples, temperature, top_k, top_p, seed):
         raise ValueError("top_p must lie in (0, 1] and be > 0 in fp32, got %r" % (top_p,))
     if seed is not None and (isinstance(seed, bool) or not isinstance(seed, numbers.Integral)):
         raise ValueError("seed must be an integer or None, got %r" % (seed,))
+
+
+def check_stochastic(beam_size, top_k, top_p):
+    """The argument checks of Generator.work(search="stochastic") beyond check_sampling's: the width gtos_sbs_step takes, and no
+    truncation -- the rule draws from the whole allowed set."""
+    if beam_size > ops.SBS_MAX_K:
+        raise ValueError("search='stochastic' takes beam_size up to %d, got %r" % (ops.SBS_MAX_K, beam_size))
+    if top_k != 0 or top_p != 1:
+        raise ValueError("top_k and top_p do not apply to search='stochastic' (got top_k = %r, top_p = %r)" % (top_k, top_p))
 
 
 def check_no_repeat_ngram(n, search, max_time_step):
@@ -59,9 +68,9 @@ def check_groups(groups, diversity, beam_size, search):
         raise ValueError("groups must be an integer >= 1, got %r" % (groups,))
     if isinstance(diversity, bool) or not isinstance(diversity, numbers.Real) or not 0 <= diversity < math.inf:
         raise ValueError("diversity must be a finite number >= 0, got %r" % (diversity,))
-    if search == "sample":
+    if search in ("sample", "stochastic"):
         if groups != 1 or diversity != 0:
-            raise ValueError("groups and diversity apply to the beam searches, not to search='sample'")
+            raise ValueError("groups and diversity apply to the beam searches, not to search=%r" % (search,))
         return 1, 0.0
     if isinstance(beam_size, bool) or not isinstance(beam_size, numbers.Integral) or beam_size < 1 or beam_size % groups:
         raise ValueError("groups must divide beam_size, got groups = %r, beam_size = %r" % (groups, beam_size))
@@ -77,8 +86,8 @@ def check_constraints(constraints, search, groups, local_idx2token, vocab):
     graph's copy tokens, or a word of ``vocab`` (the predictable-token vocabulary) with an id of its own.  -> a list of lists."""
     if constraints is None:
         return None
-    if search == "sample":
-        raise ValueError("constraints apply to the beam searches, not to search='sample'")
+    if search in ("sample", "stochastic"):
+        raise ValueError("constraints apply to the beam searches, not to search=%r" % (search,))
     if groups != 1:
         raise ValueError("constraints do not combine with groups (got groups = %r)" % (groups,))
     if isinstance(constraints, str) or not isinstance(constraints, (list, tuple)) or len(constraints) != len(local_idx2token):
@@ -112,8 +121,8 @@ def check_phrases(phrases, search, groups, constraints, coverage_penalty, local_
     its graph as in check_constraints.  A phrase may be listed twice.  -> a list of lists of lists."""
     if phrases is None:
         return None
-    if search == "sample":
-        raise ValueError("phrases apply to the beam searches, not to search='sample'")
+    if search in ("sample", "stochastic"):
+        raise ValueError("phrases apply to the beam searches, not to search=%r" % (search,))
     if groups != 1:
         raise ValueError("phrases do not combine with groups (got groups = %r)" % (groups,))
     if constraints is not None:
@@ -158,8 +167,8 @@ def check_coverage(beta, search, groups, constraints):
         return None
     if isinstance(beta, bool) or not isinstance(beta, numbers.Real) or not 0 <= beta < math.inf:
         raise ValueError("coverage_penalty must be a finite number >= 0 or None, got %r" % (beta,))
-    if search == "sample":
-        raise ValueError("coverage_penalty applies to the beam searches, not to search='sample'")
+    if search in ("sample", "stochastic"):
+        raise ValueError("coverage_penalty applies to the beam searches, not to search=%r" % (search,))
     if groups != 1:
         raise ValueError("coverage_penalty does not combine with groups (got groups = %r)" % (groups,))
     if constraints is not None:
@@ -357,7 +366,15 @@ class Generator(nn.Module):
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
         step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
         "sample": gtos_amd.search.sample_device, ``beam_size`` independent samples per graph drawn with ``temperature``, ``top_k``
-        (0 = off, at most 32) and ``top_p`` from ``seed`` (None: ops.next_seed()); these four keywords belong to "sample" only.
+        (0 = off, at most 32) and ``top_p`` from ``seed`` (None: ops.next_seed()); these four keywords belong to the sampling searches.
+        "stochastic": gtos_amd.search.stochastic_beam_search_device, stochastic beam search -- ``beam_size`` (at most 32) DISTINCT
+        sequences per graph drawn WITHOUT replacement from the distribution "sample" draws from at ``temperature`` with ``seed``
+        (``top_k`` / ``top_p`` stay at their defaults: truncation is not part of it), at the cost of a beam search of that width (the
+        rule of csrc/sbs_kernels.h; on the device by gtos_sbs_step / gtos_sbs_advance).  The first hypothesis is distributed as one
+        sample; with ``beam_size`` = 1 it is "sample"'s for the same seed.  The hypotheses are StochasticHypothesis objects in
+        descending ``gumbel``, each with ``score`` (the log-likelihood), ``logq`` (the log-probability under the distribution drawn
+        from) and ``gumbel``; gtos_amd.search.stochastic_weights gives the importance weights of an unbiased estimator.  Groups,
+        constraints, phrases and the coverage penalty do not apply to it.
         ``no_repeat_ngram`` = n > 0 (any search): no hypothesis or sample repeats an n-gram of tokens -- the continuations that would
         are scored -inf before the selection (the rule of csrc/ngram_kernels.h; on the device by gtos_ngram_block).
         ``groups`` = G > 1 ("host" and "device"): diverse beam search -- the beam_size hypotheses of a graph are G groups of
@@ -390,8 +407,8 @@ class Generator(nn.Module):
         duplicate are dropped, at most ops.AVOID_TOKENS_MAX tokens per graph remain, and an entry that one of the graph's
         ``constraints`` or ``phrases`` demands is refused (check_avoid).  A returned beam then carries ``avoid``, the entries that
         were applied, as lists of strings."""
-        if search not in ("host", "device", "sample"):
-            raise ValueError("search must be 'host', 'device' or 'sample', got %r" % (search,))
+        if search not in ("host", "device", "sample", "stochastic"):
+            raise ValueError("search must be 'host', 'device', 'sample' or 'stochastic', got %r" % (search,))
         no_repeat_ngram = check_no_repeat_ngram(no_repeat_ngram, search, max_time_step)
         groups, diversity = check_groups(groups, diversity, beam_size, search)
         coverage_penalty = check_coverage(coverage_penalty, search, groups, constraints)
@@ -402,12 +419,14 @@ class Generator(nn.Module):
                                     self.vocabs['predictable_token'])
         if avoid is not None:
             avoid = check_avoid(avoid, constraints, phrases, data['local_idx2token'], self.vocabs['predictable_token'])
-        if search == "sample":
+        if search in ("sample", "stochastic"):
             check_sampling(beam_size, temperature, top_k, top_p, seed)
+            if search == "stochastic":
+                check_stochastic(beam_size, top_k, top_p)
             if seed is None:
                 seed = ops.next_seed()
         elif (temperature, top_k, top_p, seed) != (1.0, 0, 1.0, None):
-            raise ValueError("temperature, top_k, top_p and seed apply to search='sample' only")
+            raise ValueError("temperature, top_k, top_p and seed apply to search='sample' and search='stochastic' only")
         with torch.no_grad():
             concept_repr, concept_mask, probe = self.encode_step(data, train=False)
             concept_repr = concept_repr.contiguous()
@@ -440,6 +459,8 @@ class Generator(nn.Module):
                 beam_search_device(self, memory, beams, **block)
             elif search == "sample":
                 sample_device(self, memory, beams, temperature, top_k, top_p, seed, **block)
+            elif search == "stochastic":
+                stochastic_beam_search_device(self, memory, beams, temperature, seed, **block)
             else:
                 beam_search(self, beams, memory, **block)
             if avoid is not None:

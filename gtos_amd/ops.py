@@ -1556,6 +1556,64 @@ def sample_step(t, k, V, tot, min_time_step, max_time_step, temperature, top_k, 
          int(dead_tok), ptr(dead_char), ptr(tok_out), ptr(char_out), stream())
 
 
+# ---------------------------------------------------------------------------------------------- stochastic beam search
+# (csrc/sbs.hip; gtos_amd.search.stochastic_beam_search_device drives it, the step ending with beam_reorder)
+SBS_MAX_K = 32           # MAX_K of csrc/sbs_kernels.h: the slots (distinct sequences) per graph
+
+
+def _check_sbs_cands(N, k, cand_tok, cand_ll, cand_logq, cand_gumbel):
+    """The candidate tables sbs_step writes and sbs_advance reads: [N, k] int32 / fp32 / fp64 / fp64, contiguous"""
+    require_cuda(cand_tok, cand_ll, cand_logq, cand_gumbel)
+    for x, dtype in ((cand_tok, torch.int32), (cand_ll, torch.float32), (cand_logq, torch.float64), (cand_gumbel, torch.float64)):
+        assert x.shape == (N, k) and x.dtype == dtype and x.is_contiguous()
+
+
+def sbs_step(t, k, V, tot, min_time_step, max_time_step, temperature, seed, ll, flag_shared, flag_local, owned_local, slot_logq,
+             slot_gumbel, beam_state, active, cand_tok, cand_ll, cand_logq, cand_gumbel):
+    """One stochastic-beam-search step of every live slot's row at step t (gtos_sbs_step, the rule of csrc/sbs_kernels.h): from ll
+    [N, tot] fp32 and the slots' slot_logq / slot_gumbel fp64 [N], the row's k best candidates by perturbed key into cand_tok int32
+    (-1: absent) / cand_ll fp32 / cand_logq fp64 / cand_gumbel fp64, all [N, k].  beam_state int32 [B, 4] and active are read only."""
+    require_cuda(ll, flag_shared, slot_logq, slot_gumbel, beam_state, active)
+    if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1 or ll.shape[1] != tot:
+        raise _lib.GtosHipError("sbs_step: ll must be an [N, tot] fp32 tensor with unit column stride")
+    N = ll.shape[0]
+    assert k >= 1 and N % k == 0
+    B = N // k
+    _check_sbs_cands(N, k, cand_tok, cand_ll, cand_logq, cand_gumbel)
+    assert beam_state.dtype == torch.int32 and tuple(beam_state.shape) == (B, 4)
+    assert active.numel() == 3 and active.dtype == torch.int32
+    for x in (slot_logq, slot_gumbel):
+        assert x.dtype == torch.float64 and x.numel() == N
+    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
+    for x in (flag_local, owned_local) if tot > V else ():
+        assert x is not None and x.dtype == torch.uint8 and x.numel() >= B * (tot - V)
+    for x in (flag_shared, flag_local, owned_local, slot_logq, slot_gumbel, beam_state, active):
+        assert x is None or x.is_contiguous()
+    call("gtos_sbs_step", N, k, t, V, tot, min_time_step, max_time_step, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ll),
+         max(ll.stride(0), tot), ptr(flag_shared), ptr(flag_local), ptr(owned_local), ptr(slot_logq), ptr(slot_gumbel), ptr(beam_state),
+         ptr(active), ptr(cand_tok), ptr(cand_ll), ptr(cand_logq), ptr(cand_gumbel), stream())
+
+
+def sbs_advance(t, k, V, tot, min_time_step, max_time_step, cand_tok, cand_ll, cand_logq, cand_gumbel, flag_shared, flag_local,
+                slot_score, slot_logq, slot_gumbel, beam_state, bp_parent, bp_token, comp_step, comp_parent, comp_score, comp_logq,
+                comp_gumbel, active):
+    """One advance of every graph's pool at step t (gtos_sbs_advance): the retained completions and sbs_step's candidates ranked by
+    perturbed value, the first k placed.  Updates slot_score / slot_logq / slot_gumbel fp64 [N], beam_state, bp_* row t, comp_step /
+    comp_parent int32 and comp_score / comp_logq / comp_gumbel fp64 [B, k] (descending comp_gumbel) and active in place."""
+    B, N = _check_beam_tables(k, 1, V, tot, max_time_step, cand_ll, cand_tok, flag_shared, flag_local, slot_score, beam_state, bp_parent,
+                              bp_token, comp_step, comp_parent, comp_score, active)
+    _check_sbs_cands(N, k, cand_tok, cand_ll, cand_logq, cand_gumbel)
+    require_cuda(slot_logq, slot_gumbel, comp_logq, comp_gumbel)
+    for x in (slot_logq, slot_gumbel):
+        assert x.dtype == torch.float64 and x.numel() == N and x.is_contiguous()
+    for x in (comp_logq, comp_gumbel):
+        assert x.dtype == torch.float64 and x.shape == (B, k) and x.is_contiguous()
+    call("gtos_sbs_advance", B, k, t, V, tot, min_time_step, max_time_step, ptr(cand_tok), ptr(cand_ll), ptr(cand_logq),
+         ptr(cand_gumbel), ptr(flag_shared), ptr(flag_local), ptr(slot_score), ptr(slot_logq), ptr(slot_gumbel), ptr(beam_state),
+         ptr(bp_parent), ptr(bp_token), ptr(comp_step), ptr(comp_parent), ptr(comp_score), ptr(comp_logq), ptr(comp_gumbel),
+         ptr(active), stream())
+
+
 # ---------------------------------------------------------------------------------------------- repeat-n-gram blocking
 # (csrc/ngram.hip; gtos_amd.search._slot_decode launches it for both device decoders)
 NGRAM_MAX_T = 4096       # MAX_T of csrc/ngram_kernels.h: the longest history row the kernel stages

@@ -35,6 +35,10 @@ words and phrases the output of a graph must not hold, banned in ll before the s
 
 ``sample_device`` decodes by sampling instead (csrc/sample.hip): the same fixed slots, one independent sample per slot with
 temperature / top-k / top-p, and Beam objects filled the same way.
+
+``stochastic_beam_search_device`` samples WITHOUT replacement (csrc/sbs.hip, the rule in csrc/sbs_kernels.h): the slots, tables and
+reorder of the beam search, the selection by perturbed values, k distinct sequences per graph with the quantities an estimator needs
+(``stochastic_weights``).
 """
 import math
 import types
@@ -939,6 +943,100 @@ def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_ev
                         tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)
     return _slot_decode("sample_device", model, memory, beams, sync_every, stats, 1, None, layout, step, fill_samples, no_repeat_ngram,
                         lambda d, t: (None, d.arr['tokens'][t]), avoid=avoid_ids(model, memory['local_idx2token'], avoid))
+
+
+class StochasticHypothesis(Hypothesis):
+    __slots__ = ("logq", "gumbel")
+
+    def __init__(self, seq, score, logq, gumbel):
+        super().__init__(seq, score)
+        self.logq = logq                # log-probability under the distribution drawn from: tempered, locally normalised over the allowed tokens
+        self.gumbel = gumbel            # the perturbed value G the hypothesis was ranked by
+
+
+def stochastic_roots(seed, B):
+    """root_gumbel of csrc/sbs_kernels.h for graphs 0 .. B-1 as numpy fp64: the perturbed value of every graph's empty prefix, a
+    Gumbel(0) draw from column 0 of the hash row of (seed, graph, slot index ops.SBS_MAX_K -- which no slot has --, step 0)."""
+    import numpy as np
+    from .synth import SplitMix64
+    graphs = SplitMix64(int(seed) & 0xFFFFFFFFFFFFFFFF).u64(B) if B else np.zeros(0, np.uint64)
+    bits = np.array([SplitMix64(int(SplitMix64(int(SplitMix64(int(g)).u64(ops.SBS_MAX_K + 1)[-1])).u64(1)[0])).u64(1)[0] for g in graphs],
+                    dtype=np.uint64)
+    u = ((bits >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+    return -np.log(-np.log(np.where(u < 1.0, u, 1.0 - 2.0 ** -53)))
+
+
+def stochastic_beam_search_device(model, memory, beams, temperature, seed, sync_every=8, stats=None, no_repeat_ngram=0, avoid=None):
+    """Stochastic beam search on the device (csrc/sbs.hip, the rule in csrc/sbs_kernels.h; Kool, van Hoof and Welling 2019): every
+    graph gets ``beam_size`` DISTINCT sequences drawn without replacement from the distribution ``sample_device`` draws one sequence
+    from at this temperature (top_k = 0, top_p = 1; <UNK>, other graphs' copy ids and <END> before min_time_step are never drawn), at
+    the cost of a beam search of that width.  The slots, the back-pointer, completion and state tables and the reorder are those of
+    beam_search_device; the selection is gtos_sbs_step (per live row the k best candidates by perturbed key, from the counter hash of
+    (seed, graph, slot, step, column); the empty prefix's value is stochastic_roots(seed, B)) and gtos_sbs_advance (the graph's completions and candidates ranked by perturbed value:
+    finished hypotheses keep competing until the search ends).  ``sync_every``, ``stats`` and ``no_repeat_ngram`` as in _slot_decode,
+    ``avoid`` as in beam_search_device: a banned column is not allowed, and the distribution is normalised over what is left.
+    Returns the beams filled with StochasticHypothesis objects (score = the fp64 sum of the model's ll, logq, gumbel):
+    completed_hypotheses (ended by <END>) and hypotheses (cut at max_time_step), each in descending gumbel; together min(k, number of
+    allowed sequences) of them.  stochastic_weights turns a beam into importance weights."""
+    tables = types.SimpleNamespace()                         # the candidate tables, which the host never reads
+
+    def layout(d):
+        c, dev = tables, memory['probe'].device
+        c.owned = model.sample_tables(d.local, d.tot)
+        c.root = torch.from_numpy(stochastic_roots(seed, d.B)).to(dev)
+        c.tok = torch.full((d.N, d.k), -1, dtype=torch.int32, device=dev)
+        c.ll = torch.zeros((d.N, d.k), dtype=torch.float32, device=dev)
+        c.logq, c.gumbel = (torch.zeros((d.N, d.k), dtype=torch.float64, device=dev) for _ in range(2))
+        return _plain_cuts(d, d.B, dbls=[('slot_logq', (d.N,), 0), ('slot_gumbel', (d.N,), 0), ('comp_logq', (d.B, d.k), 0),
+                                         ('comp_gumbel', (d.B, d.k), 0)])
+
+    def step(d, t, ll, cur, nxt, tok_out, char_out):
+        a, c, tab = d.arr, tables, d.tab
+        if t == 0:
+            a['slot_gumbel'].view(d.B, d.k)[:, 0] = c.root
+        ops.sbs_step(t, d.k, d.V, d.tot, d.min_t, d.max_t, temperature, seed, ll, tab['flag_shared'], tab['flag_local'], c.owned,
+                     a['slot_logq'], a['slot_gumbel'], a['state'], a['active'], c.tok, c.ll, c.logq, c.gumbel)
+        ops.sbs_advance(t, d.k, d.V, d.tot, d.min_t, d.max_t, c.tok, c.ll, c.logq, c.gumbel, tab['flag_shared'], tab['flag_local'],
+                        a['slot_score'], a['slot_logq'], a['slot_gumbel'], a['state'], a['bp_parent'], a['bp_token'], a['comp_step'],
+                        a['comp_parent'], a['comp_score'], a['comp_logq'], a['comp_gumbel'], a['active'])
+        _plain_reorder(d, t, cur, nxt, tok_out, char_out)
+    _slot_decode("stochastic_beam_search_device", model, memory, beams, sync_every, stats, 2, 1, layout, step, fill_stochastic,
+                 no_repeat_ngram, _taken, avoid=avoid_ids(model, memory['local_idx2token'], avoid))
+    for b, beam in enumerate(beams):
+        if beam.steps == 0:
+            beam.hypotheses = [StochasticHypothesis([STR], 0., 0., float(stochastic_roots(seed, b + 1)[b]))]
+    return beams
+
+
+def fill_stochastic(beams, k, state, slot_logq, slot_gumbel, comp_logq, comp_gumbel, **plain):
+    """The Beam objects of a stochastic beam search from its tables (flat lists): fill_beams, every hypothesis a StochasticHypothesis
+    with the logq / gumbel of its completion row (comp_* [B*k]) or slot (slot_* [N]).  Both lists are in descending gumbel."""
+    fill_beams(beams, k, state=state, **plain)
+    for b, beam in enumerate(beams):
+        if not state[4 * b]:
+            continue
+        beam.completed_hypotheses = [StochasticHypothesis(h.seq, h.score, comp_logq[b * k + j], comp_gumbel[b * k + j])
+                                     for j, h in enumerate(beam.completed_hypotheses)]
+        beam.hypotheses = [StochasticHypothesis(h.seq, h.score, slot_logq[b * k + j], slot_gumbel[b * k + j])
+                           for j, h in enumerate(beam.hypotheses)]
+    return beams
+
+
+def stochastic_weights(beam):
+    """The importance weights that make a stochastic beam search's sample an estimator (Kool et al. 2019, section 4.2): with kappa the
+    smallest ``gumbel`` of the beam's hypotheses (finished and unfinished), every hypothesis h with gumbel > kappa gets
+    w = q(h) / P(G_h > kappa) = exp(logq) / (1 - exp(-exp(logq - kappa))), and sum_h w_h f(h) is an unbiased estimate of E_q[f].
+    -> ([(hypothesis, w), ...] in descending gumbel, kappa); a beam with one hypothesis has no threshold below it: ([], its gumbel)."""
+    hyps = sorted(list(beam.completed_hypotheses) + list(beam.hypotheses), key=lambda h: h.gumbel, reverse=True)
+    if not hyps:
+        return [], float('inf')
+    kappa = hyps[-1].gumbel
+    def weight(logq):
+        above = logq - kappa                                 # past exp's range the probability of inclusion is 1, or exp(above), in fp64
+        if above < -700.0:
+            return math.exp(kappa)
+        return math.exp(logq) / -math.expm1(-math.exp(above)) if above < 700.0 else math.exp(logq)
+    return [(h, weight(h.logq)) for h in hyps if h.gumbel > kappa], kappa
 
 
 def fill_samples(beams, k, state, tokens, score, token_string):

@@ -617,6 +617,43 @@ int gtos_avoid_block(int N, int k, int t, int tot, float* ll, int64_t ld, const 
                      const uint64_t* init, const uint64_t* last, const int* n_pos, const uint64_t* state_prev,
                      uint64_t* state_cur, const int* active, void* stream);
 
+/* ---- Stochastic beam search on the device (ABI 32; csrc/sbs.hip, the rule in csrc/sbs_kernels.h), driven by
+ * gtos_amd.search.stochastic_beam_search_device: k DISTINCT sequences per graph drawn without replacement from the tempered, locally
+ * normalised model distribution q (Kool, van Hoof and Welling 2019, "Stochastic Beams and Where to Find Them": Gumbel-top-k over the
+ * prefix tree), at the cost of a beam search of width k.  B graphs x k slots as in gtos_beam_advance, N = B*k; beside slot_score a live
+ * slot carries slot_logq (log q of its prefix) and slot_gumbel (its perturbed value G), all fp64 [N].  At the start beam_state is
+ * {0, 0, 1, 0} per graph and slot 0 of graph b has score = logq = 0 and G = a Gumbel(0) draw of the caller's (root_gumbel(seed, b) in
+ * csrc/sbs_kernels.h; with 0 instead the draw follows the same law but the values no longer support importance weights).  The rule has no counterpart in generator/search.py.  Per step: gtos_ngram_block /
+ * gtos_avoid_block if asked (a banned column is not allowed), _step, _advance, gtos_beam_reorder (the tables keep its format).
+ * _step (one workgroup per slot row of ll [N, tot] fp32, row stride ld >= tot): slot s = (b, j) is live when beam_state[b] is not
+ *   done and j < #live.  Its allowed columns are gtos_sample_step's (finite ll; not <UNK>; copy ids the graph owns, owned_local uint8
+ *   [B, tot-V]; <END> only once t >= min_time_step).  With m the largest allowed ll and lse = log sum exp((ll_c - m) / temperature),
+ *   logq_c = slot_logq[s] + (ll_c - m) / temperature - lse and key_c = logq_c + g_c, g_c the Gumbel variate gtos_sample_step draws for
+ *   (seed, b, j, t, c).  The k columns with the largest key (then the lower column) are the row's candidates, Z the largest key:
+ *   cand_tok int32 [N,k] (the column; -1 from the number of allowed columns on), cand_ll fp32 [N,k], cand_logq fp64 [N,k] and
+ *   cand_gumbel fp64 [N,k] = -log(exp(-G_s) - exp(-Z) + exp(-key_c)), exactly G_s for the first.  A dead slot, or a step whose active
+ *   word is clear, writes nothing.  active int32 [3] as in csrc/slot_kernels.h, read only.
+ *   SHAPES (-10 outside): 1 <= k <= 32, N % k == 0, 0 <= t < max_time_step, 1 <= V <= tot <= ld, 0 < temperature < inf; -23 for a
+ *   null pointer (flag_local and owned_local may be null when tot == V).
+ * _advance (one workgroup per graph): the pool of graph b is its #completed completion rows with their comp_gumbel, then the present
+ *   candidates of its live slots in (slot, rank) order; it is ranked by larger G, then earlier position, and the first k stay.  A kept
+ *   <END> candidate becomes a completion (comp_step = t, comp_parent = its slot, comp_score = slot_score + ll, comp_logq,
+ *   comp_gumbel), any other the next live slot in rank order (row t of bp_parent / bp_token, slot_score, slot_logq, slot_gumbel); a
+ *   completion outside the first k is dropped.  The completion rows ([B,k]) are rewritten in descending G, so #completed + #live <= k.
+ *   beam_state int32 [B,4] = steps, #completed, #live, done; done = no live slot left or steps == max_time_step.  active: the flag is
+ *   "some not-done graph has a live slot".
+ *   SHAPES (-10 outside): 1 <= k <= 32, 0 <= t < max_time_step, 1 <= V <= tot; -23 for a null pointer (flag_local may be null when
+ *   tot == V). */
+int gtos_sbs_step(int N, int k, int t, int V, int tot, int min_time_step, int max_time_step, float temperature, uint64_t seed,
+                  const float* ll, int64_t ld, const uint8_t* flag_shared, const uint8_t* flag_local, const uint8_t* owned_local,
+                  const double* slot_logq, const double* slot_gumbel, const int* beam_state, const int* active, int* cand_tok,
+                  float* cand_ll, double* cand_logq, double* cand_gumbel, void* stream);
+int gtos_sbs_advance(int B, int k, int t, int V, int tot, int min_time_step, int max_time_step, const int* cand_tok,
+                     const float* cand_ll, const double* cand_logq, const double* cand_gumbel, const uint8_t* flag_shared,
+                     const uint8_t* flag_local, double* slot_score, double* slot_logq, double* slot_gumbel, int* beam_state,
+                     int* bp_parent, int* bp_token, int* comp_step, int* comp_parent, double* comp_score, double* comp_logq,
+                     double* comp_gumbel, int* active, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
