@@ -50,6 +50,29 @@ def check_stochastic(beam_size, top_k, top_p):
         raise ValueError("top_k and top_p do not apply to search='stochastic' (got top_k = %r, top_p = %r)" % (top_k, top_p))
 
 
+def check_truncation(search, min_p, typical_p, epsilon_cutoff, eta_cutoff):
+    """The argument checks of Generator.work(min_p=, typical_p=, epsilon_cutoff=, eta_cutoff=): ValueError unless every value lies in
+    its range as the fp32 value gtos_truncate_block takes (min_p in [0, 1], typical_p in (0, 1], the cutoffs in [0, 1)), a value
+    other than "off" stays one in fp32, and anything but the defaults comes with search="sample".  -> the cuts that are on, as the
+    keywords of search.sample_device (empty: the call as it always was)."""
+    given = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+    off = dict(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
+    ranges = dict(min_p=("[0, 1] (0 = off)", lambda f: 0 <= f <= 1), typical_p=("(0, 1] (1 = off)", lambda f: 0 < f <= 1),
+                  epsilon_cutoff=("[0, 1) (0 = off)", lambda f: 0 <= f < 1), eta_cutoff=("[0, 1) (0 = off)", lambda f: 0 <= f < 1))
+    on = {}
+    for name, v in given.items():
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError("%s must be a number in %s, got %r" % (name, ranges[name][0], v))
+        f = ctypes.c_float(v).value                                               # the kernel takes it as fp32
+        if not ranges[name][1](f) or (v == off[name]) != (f == off[name]):
+            raise ValueError("%s must lie in %s as an fp32 value, got %r" % (name, ranges[name][0], v))
+        if v != off[name]:
+            on[name] = float(v)
+    if on and search != "sample":
+        raise ValueError("%s apply to search='sample' only, not to search=%r" % (", ".join(sorted(on)), search))
+    return on
+
+
 def check_no_repeat_ngram(n, search, max_time_step):
     """The argument check of Generator.work(no_repeat_ngram=): ValueError unless n is an integer >= 0 and, for the device searches,
     n and the step count fit the history row gtos_ngram_block stages (ops.NGRAM_MAX_T)."""
@@ -361,7 +384,7 @@ class Generator(nn.Module):
     # ------------------------------------------------------------------------------------------------ inference
     def work(self, data, beam_size, max_time_step, min_time_step=1, search="host", *, temperature=1.0, top_k=0, top_p=1.0,
              seed=None, no_repeat_ngram=0, groups=1, diversity=0.0, constraints=None, coverage_penalty=None, phrases=None,
-             avoid=None):
+             avoid=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
         """Beam search for every graph of the batch (generator.py:96-110).  Returns the finished Beam objects
         (``beam.get_k_best(k, alpha)``).  search="host": gtos_amd.search.beam_search (selection on the host, one read per
         step); "device": gtos_amd.search.beam_search_device (fixed hypothesis slots, selection and cache reorder on the GPU);
@@ -406,7 +429,17 @@ class Generator(nn.Module):
         gtos_amd.search.avoided_tokens).  The strings resolve as for ``constraints``; an entry the graph cannot produce and a
         duplicate are dropped, at most ops.AVOID_TOKENS_MAX tokens per graph remain, and an entry that one of the graph's
         ``constraints`` or ``phrases`` demands is refused (check_avoid).  A returned beam then carries ``avoid``, the entries that
-        were applied, as lists of strings."""
+        were applied, as lists of strings.
+        ``min_p``, ``typical_p``, ``epsilon_cutoff``, ``eta_cutoff`` ("sample" only; any other search, "stochastic" included, refuses
+        a value other than the default): cuts of the sampled distribution that follow each step's own shape, where ``top_k`` /
+        ``top_p`` are fixed (the rule of csrc/truncate_kernels.h; on the device by gtos_truncate_block, one launch per step in front
+        of gtos_sample_step, none with the defaults).  On the tempered distribution over the allowed tokens, in this order, each on the
+        renormalised survivors of the one before: ``min_p`` in (0, 1] (0 = off) keeps the tokens with at least ``min_p`` times the
+        probability of the likeliest one; ``typical_p`` in (0, 1) (1 = off), locally typical sampling, keeps the tokens whose
+        information content lies nearest the entropy, up to a ``typical_p`` share of the mass; ``epsilon_cutoff`` e and
+        ``eta_cutoff`` h in [0, 1) (0 = off) keep the tokens of probability >= max(e, min(h, sqrt(h) exp(-entropy))) and always the
+        likeliest.  ``top_k`` / ``top_p`` then act on what is left -- other toolkits apply ``top_k`` / ``top_p`` first.  The bans of
+        ``no_repeat_ngram`` and ``avoid`` come before all of them.  Scores stay log-likelihoods (check_truncation)."""
         if search not in ("host", "device", "sample", "stochastic"):
             raise ValueError("search must be 'host', 'device', 'sample' or 'stochastic', got %r" % (search,))
         no_repeat_ngram = check_no_repeat_ngram(no_repeat_ngram, search, max_time_step)
@@ -427,6 +460,7 @@ class Generator(nn.Module):
                 seed = ops.next_seed()
         elif (temperature, top_k, top_p, seed) != (1.0, 0, 1.0, None):
             raise ValueError("temperature, top_k, top_p and seed apply to search='sample' and search='stochastic' only")
+        cuts = check_truncation(search, min_p, typical_p, epsilon_cutoff, eta_cutoff)
         with torch.no_grad():
             concept_repr, concept_mask, probe = self.encode_step(data, train=False)
             concept_repr = concept_repr.contiguous()
@@ -458,7 +492,7 @@ class Generator(nn.Module):
             if search == "device":
                 beam_search_device(self, memory, beams, **block)
             elif search == "sample":
-                sample_device(self, memory, beams, temperature, top_k, top_p, seed, **block)
+                sample_device(self, memory, beams, temperature, top_k, top_p, seed, **block, **cuts)      # no cut: the call as it always was
             elif search == "stochastic":
                 stochastic_beam_search_device(self, memory, beams, temperature, seed, **block)
             else:

@@ -1532,7 +1532,7 @@ def diverse_reorder(src, dst, t, k, width, bp_parent, bp_token, group_state, act
 
 
 # ---------------------------------------------------------------------------------------------- device-resident sampling decode
-# (csrc/sample.hip; gtos_amd.search.sample_device drives it)
+# (csrc/sample.hip, csrc/truncate.hip; gtos_amd.search.sample_device drives it)
 def sample_step(t, k, V, tot, min_time_step, max_time_step, temperature, top_k, top_p, seed, ll, flag_shared, flag_local, owned_local,
                 score, slot_state, tokens, active, tok_shared, tok_local, char_shared, char_local, dead_tok, dead_char, tok_out,
                 char_out):
@@ -1554,6 +1554,27 @@ def sample_step(t, k, V, tot, min_time_step, max_time_step, temperature, top_k, 
          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ll), max(ll.stride(0), tot), ptr(flag_shared), ptr(flag_local), ptr(owned_local),
          ptr(score), ptr(slot_state), ptr(tokens), ptr(active), ptr(tok_shared), ptr(tok_local), ptr(char_shared), ptr(char_local), C,
          int(dead_tok), ptr(dead_char), ptr(tok_out), ptr(char_out), stream())
+
+
+def truncate_block(t, k, V, tot, min_time_step, temperature, min_p, typical_p, epsilon_cutoff, eta_cutoff, ll, flag_shared, flag_local,
+                   owned_local, slot_state, active):
+    """Before the sample_step of step t >= 0 (gtos_truncate_block, the rule of csrc/truncate_kernels.h): in every live slot's row of
+    ll [N, tot] fp32 the allowed columns that the min_p, typical_p and epsilon_cutoff / eta_cutoff cuts remove are set to -inf, in
+    place; at least one cut is on.  slot_state int32 [N, 3] and active are read only; dead slots' rows are left alone."""
+    require_cuda(ll, flag_shared, slot_state, active)
+    if ll.dim() != 2 or ll.dtype != torch.float32 or ll.stride(1) != 1:
+        raise _lib.GtosHipError("truncate_block: ll must be a 2-D fp32 tensor with unit column stride")
+    N = ll.shape[0]
+    assert ll.shape[1] == tot and k >= 1 and N % k == 0
+    assert slot_state.shape == (N, 3) and slot_state.dtype == torch.int32 and active.numel() == 3 and active.dtype == torch.int32
+    assert flag_shared.dtype == torch.uint8 and flag_shared.numel() >= V
+    for x in (flag_local, owned_local) if tot > V else ():
+        assert x is not None and x.dtype == torch.uint8 and x.numel() >= N // k * (tot - V)
+    for x in (flag_shared, flag_local, owned_local, slot_state, active):
+        assert x is None or x.is_contiguous()
+    call("gtos_truncate_block", N, k, t, V, tot, min_time_step, float(temperature), float(min_p), float(typical_p),
+         float(epsilon_cutoff), float(eta_cutoff), ptr(ll), max(ll.stride(0), tot), ptr(flag_shared), ptr(flag_local),
+         ptr(owned_local), ptr(slot_state), ptr(active), stream())
 
 
 # ---------------------------------------------------------------------------------------------- stochastic beam search

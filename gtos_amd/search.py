@@ -923,7 +923,8 @@ def sample_bits(seed, graph, sample, t, cols):
     return SplitMix64(key).u64(int(cols.max()) + 1 if cols.size else 0)[cols]
 
 
-def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_every=8, stats=None, no_repeat_ngram=0, avoid=None):
+def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_every=8, stats=None, no_repeat_ngram=0, avoid=None,
+                  min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
     """Sampling decode on the device (csrc/sample.hip), the counterpart of beam_search_device with the same ``memory``: every graph
     gets ``beam_size`` independent samples in fixed slots (slot s is sample s % k of graph s // k), each drawing its next token by the
     rule of csrc/sample_kernels.h (temperature, top_k, top_p; <UNK>, other graphs' copy ids and <END> before min_time_step are never
@@ -931,13 +932,25 @@ def sample_device(model, memory, beams, temperature, top_k, top_p, seed, sync_ev
     [max_time_step, N, 2d] cache and nothing is reordered; ``sync_every``, ``stats`` and ``no_repeat_ngram`` as in _slot_decode, ``avoid`` as in
     beam_search_device.  Returns the beams filled
     like a beam search's: completed_hypotheses (ended by <END>) by completion step, then sample index; hypotheses (unfinished) in
-    sample order; score = the fp64 sum of the model's ll of the drawn tokens."""
+    sample order; score = the fp64 sum of the model's ll of the drawn tokens.
+    ``min_p`` (0 = off), ``typical_p`` (1 = off), ``epsilon_cutoff`` / ``eta_cutoff`` (0 = off): the cuts of csrc/truncate_kernels.h,
+    which depend on each row's maximum, entropy and normaliser.  With one of them on (as the fp32 value the kernel takes), every step
+    launches gtos_truncate_block after the bans and directly before gtos_sample_step: it removes columns from the row in that order
+    (min-p, typical, epsilon / eta, each on the renormalised survivors), and ``top_k`` / ``top_p`` then act on what is left -- other
+    toolkits apply top_k / top_p first.  With all four at their defaults nothing more is launched."""
+    import ctypes
+    cuts = tuple(ctypes.c_float(v).value for v in (min_p, typical_p, epsilon_cutoff, eta_cutoff))
+    truncate = cuts != (0.0, 1.0, 0.0, 0.0)
+
     def layout(d):
         d.owned = model.sample_tables(d.local, d.tot)
         return [('state', (d.N, 3), (0, -1, 0)), ('tokens', (d.max_t, d.N), -1)], [('score', (d.N,), 0)]      # -1: no completion yet
 
     def step(d, t, ll, cur, nxt, tok_out, char_out):
         a, tab = d.arr, d.tab
+        if truncate:
+            ops.truncate_block(t, d.k, d.V, d.tot, d.min_t, temperature, *cuts, ll, tab['flag_shared'], tab['flag_local'], d.owned,
+                               a['state'], a['active'])
         ops.sample_step(t, d.k, d.V, d.tot, d.min_t, d.max_t, temperature, top_k, top_p, seed, ll, tab['flag_shared'], tab['flag_local'],
                         d.owned, a['score'], a['state'], a['tokens'], a['active'], tab['tok_shared'], tab['tok_local'],
                         tab['char_shared'], tab['char_local'], tab['dead_tok'], tab['dead_char'], tok_out, char_out)

@@ -654,6 +654,28 @@ int gtos_sbs_advance(int B, int k, int t, int V, int tot, int min_time_step, int
                      int* bp_parent, int* bp_token, int* comp_step, int* comp_parent, double* comp_score, double* comp_logq,
                      double* comp_gumbel, int* active, void* stream);
 
+/* ---- Distribution-shaped truncation of the sampling decode (ABI 33; csrc/truncate.hip, the rule in csrc/truncate_kernels.h), driven
+ * by gtos_amd.search.sample_device(min_p=, typical_p=, epsilon_cutoff=, eta_cutoff=): the min-p cut, locally typical sampling (Meister
+ * et al. 2023) and the epsilon / eta cutoffs (Hewitt et al. 2022), which depend on each row's maximum, entropy and normaliser.  The
+ * rule has no counterpart in generator/search.py; it is stated in full in csrc/truncate_kernels.h.
+ * _block (one workgroup per slot row) is launched once per step t >= 0, after the decoder's ll [N, tot] fp32 (row stride ld >= tot)
+ *   and gtos_ngram_block / gtos_avoid_block, directly before gtos_sample_step, whose arguments of the same name it shares.  A slot is
+ *   live when active[t % 3] is set and slot_state[s, 2] (dead) is clear; both are read only.  On a live row, A = the allowed columns
+ *   of gtos_sample_step (finite ll; not <UNK>; copy ids the graph owns; <END> only once t >= min_time_step), x = ll / temperature in
+ *   fp64, and in this order, each stage on the renormalised survivors of the one before:
+ *   min_p in (0, 1] (0 = off) keeps x >= max x + log(min_p); typical_p in (0, 1) (1 = off) keeps the columns whose information
+ *   content lies nearest the entropy H, dev = |-log p - H| as fp32 ascending, up to the smallest dev whose set holds a typical_p share
+ *   of the mass (ties kept); epsilon_cutoff e and eta_cutoff h in [0, 1) (0 = off) keep p' >= max(e, min(h, sqrt(h) exp(-H'))) and
+ *   always the best survivor.  Every column of A that did not survive gets ll = -inf, in place; columns outside A, survivors, rows
+ *   with empty A, dead rows, a step that does not run and everything in [tot, ld) stay bit for bit.  The set is never empty when A
+ *   is not.  top_k / top_p of gtos_sample_step then act on what is left (other toolkits apply them first).
+ *   SHAPES (-10 outside): the ranges above with at least one cut on, k >= 1, N % k == 0, t >= 0, 1 <= V <= tot <= ld,
+ *   0 < temperature < inf; -23 for a null pointer (flag_local and owned_local may be null when tot == V); 0 for N <= 0. */
+int gtos_truncate_block(int N, int k, int t, int V, int tot, int min_time_step, float temperature, float min_p, float typical_p,
+                        float epsilon_cutoff, float eta_cutoff, float* ll, int64_t ld, const uint8_t* flag_shared,
+                        const uint8_t* flag_local, const uint8_t* owned_local, const int* slot_state, const int* active,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
