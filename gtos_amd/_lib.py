@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgtos_hip.so")
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 c_p, c_i, c_l, c_f, c_u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
 
@@ -66,6 +66,7 @@ SIGNATURES = {
     "gtos_copy_nll_ls_bwd": [c_i] * 5 + [c_p, c_l, c_p, c_p, c_p, c_l, c_f, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "gtos_copy_eval_fwd": [c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p],
     "gtos_eval_accumulate": [c_i, c_i, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p],
+    "gtos_copy_explain_fwd": [c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_l] + [c_p] * 10,
     "gtos_beam_topk": [c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p],
     "gtos_beam_advance": [c_i] * 7 + [c_p] * 13,
     "gtos_beam_reorder": [c_i, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_l, c_p, c_p,

@@ -83,6 +83,17 @@ class TokenGenerator(nn.Module):
         """Teacher-forced scoring beside ``forward``: the same attention, LayerNorm and projections without dropout, then ONE kernel
         (gtos_copy_eval_fwd) for what a scorer reads off decoder.py's ll row: (nll [T,B] fp32 -- the plain -log p(target), label
         smoothing does not enter --, pred [T,B] int32 = the row's argmax, p_pred [T,B] fp32)."""
+        logits, div, alignment_weight = self._mixture_operands(outs, graph_state, graph_padding_mask)
+        return ops.copy_eval(logits, div, alignment_weight, copy_seq, target, self.vocabs['predictable_token'].padding_idx)
+
+    def explain(self, outs, graph_state, graph_padding_mask, copy_seq, target):
+        """Token-level attribution beside ``evaluate``, on the same operands: ONE kernel (gtos_copy_explain_fwd) for the nine [T,B]
+        tensors of ops.copy_explain (nll, entropy, gate, copy_share, source, source_weight, focus, focus_weight, rank)."""
+        logits, div, alignment_weight = self._mixture_operands(outs, graph_state, graph_padding_mask)
+        return ops.copy_explain(logits, div, alignment_weight, copy_seq, target, self.vocabs['predictable_token'].padding_idx)
+
+    def _mixture_operands(self, outs, graph_state, graph_padding_mask):
+        """(logits [T,B,V], div [T,B,2], alignment weights [T,B,n]) of the full-sequence pass without dropout."""
         cd = self.alignment_layer.compute_dtype
         outs_s, outs = ops.split_stream(outs, cd)
         x, alignment_weight = self.alignment_layer(outs, graph_state, graph_state, key_padding_mask=graph_padding_mask,
@@ -92,7 +103,7 @@ class TokenGenerator(nn.Module):
         hidden = torch.tanh(ops.linear(outs, self.transfer.weight, self.transfer.bias))
         logits = _padded_linear(hidden, self.generator)
         div = _padded_linear(hidden, self.diverter)
-        return ops.copy_eval(logits, div, alignment_weight, copy_seq, target, self.vocabs['predictable_token'].padding_idx)
+        return logits, div, alignment_weight
 
 
 class DecodeLayer(nn.Module):
@@ -121,6 +132,13 @@ class DecodeLayer(nn.Module):
         outs = self.inference_core(probe, kv=snt_state, self_padding_mask=snt_padding_mask, self_attn_mask=attn_mask,
                                    external_memories=graph_state, external_padding_mask=graph_padding_mask)
         return self.token_generator.evaluate(outs, graph_state, graph_padding_mask, copy_seq, target)
+
+    def explain(self, probe, graph_state, snt_state, graph_padding_mask, snt_padding_mask, attn_mask, copy_seq, target):
+        """``evaluate`` with TokenGenerator.explain at the end: the nine attribution tensors per target position.  Call it in eval
+        mode under no_grad (Generator.explain does)."""
+        outs = self.inference_core(probe, kv=snt_state, self_padding_mask=snt_padding_mask, self_attn_mask=attn_mask,
+                                   external_memories=graph_state, external_padding_mask=graph_padding_mask)
+        return self.token_generator.explain(outs, graph_state, graph_padding_mask, copy_seq, target)
 
     def step(self, probe, token_row, caches, mem, want_align=False):
         """Log-likelihoods of the next token, [1,N,V+ext] (decoder.py:85-87 with work=True), for N live hypotheses.

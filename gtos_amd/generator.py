@@ -9,6 +9,7 @@ exact same function as the reference's ``relation.index_select(0, idx).view(n,n,
 reference's signature (generator.py:119) for callers that bring their own search loop.
 """
 import collections
+import contextlib
 import ctypes
 import math
 import numbers
@@ -263,6 +264,51 @@ class Scores(collections.namedtuple("Scores", "sentence_ll tokens correct token_
         local, vocab = data['local_idx2token'], vocab if vocab is not None else self.vocab
         pred, owner, n_tok = self.pred.t().tolist(), self.graph_of.tolist(), self.tokens.tolist()
         return [[local[g][i] if i in local[g] else vocab.idx2token(i) for i in row[:n]] for row, g, n in zip(pred, owner, n_tok)]
+
+
+class Explained(collections.namedtuple("Explained", "token_ll entropy copy_gate copy_share source source_weight focus focus_weight rank "
+                                                    "tokens graph_of")):
+    """What Generator.explain returns, all DEVICE tensors over N sequences of at most T target positions (tokens + <END>).  Per
+    position [T,N]: token_ll fp32 (log p of the target, bitwise Generator.score's; 0 at padding), entropy fp32 (of the generate/copy
+    mixture over the vocabulary and the graph's copy ids, nats), copy_gate fp32, copy_share fp32 (the part of the target's probability
+    that was copied from the graph), source int32 / source_weight fp32 (the graph node the target was copied from: the heaviest
+    alignment among the nodes whose copy id is the target; -1 / 0 when no node holds it), focus int32 / focus_weight fp32 (the node
+    the alignment is heaviest on, whatever its id) and rank int32 (how many outputs the model put strictly above the target; 0: it
+    was the argmax; -1: the model cannot produce it).  At padding: copy_share 0, source -1, source_weight 0, rank -1.  ``source`` and
+    ``focus`` index the graph-state axis: row s of ``data['cp_seq'][:, graph_of]``, the axis of ``Coverage.coverage``.
+    tokens [N] int32 (target positions), graph_of [N] int64 (the graph each sequence was explained against)."""
+    vocab = None             # the predictable-token vocabulary,
+    concept_vocab = None     # the concept vocabulary and
+    target = None            # the target ids [T,N] int64 that were explained (Generator.explain sets the three on the instance)
+
+    def rows(self, data, vocab=None, concept_vocab=None):
+        """Host side, on demand (the one host read): per sequence a list of per-token dicts, padded positions skipped -- ``token``
+        (a copy id through the graph's ``data['local_idx2token']``, anything else through the predictable-token vocabulary), ``ll``,
+        ``entropy``, ``copy_gate``, ``copy_share``, ``rank``, ``source`` and ``focus`` (graph-state positions, -1: none) and, where
+        ``data`` carries the concept ids, ``source_concept`` / ``focus_concept``: the strings of those two nodes (None at -1)."""
+        local, vocab = data['local_idx2token'], vocab if vocab is not None else self.vocab
+        concept_vocab = concept_vocab if concept_vocab is not None else self.concept_vocab
+        concept = data.get('concept') if concept_vocab is not None else None
+        if concept is not None:
+            concept = concept.t().tolist()                 # per graph <CLS> and then its nodes: position s is entry s + 1
+        target = data['token_out'] if self.target is None else self.target
+        cols = [v.t().tolist() for v in (target, self.token_ll, self.entropy, self.copy_gate, self.copy_share, self.rank, self.source,
+                                         self.focus)]
+        owner, n_tok = self.graph_of.tolist(), self.tokens.tolist()
+
+        def node(g, s):
+            return None if s < 0 else concept_vocab.idx2token(concept[g][s + 1])
+        out = []
+        for j, (g, n) in enumerate(zip(owner, n_tok)):
+            seq = []
+            for y, ll, ent, gate, share, rank, src, foc in zip(*(c[j][:n] for c in cols)):
+                d = {"token": local[g][y] if y in local[g] else vocab.idx2token(y), "ll": ll, "entropy": ent, "copy_gate": gate,
+                     "copy_share": share, "rank": rank, "source": src, "focus": foc}
+                if concept is not None:
+                    d["source_concept"], d["focus_concept"] = node(g, src), node(g, foc)
+                seq.append(d)
+            out.append(seq)
+        return out
 
 
 class Generator(nn.Module):
@@ -532,6 +578,13 @@ class Generator(nn.Module):
         """The device part of ``score``: (nll [T,N] fp32, pred [T,N] int32, p_pred [T,N] fp32, target [T,N] int64, graph_of [N]
         int64).  Eval mode and no autograd whatever the module's state, which is left as found; no dropout seed is drawn."""
         given = None if targets is None else self._score_sequences(data, targets)
+        with self._as_scorer():
+            return self._score_rows(data, given)
+
+    @contextlib.contextmanager
+    def _as_scorer(self):
+        """Eval mode under no_grad for a teacher-forced post-pass (score, coverage, explain); the module's mode and the relation
+        encoder's ``trie_in_eval`` are put back as found."""
         modes = [(m, m.training) for m in self.modules()]
         enc = self.relation_encoder
         trie_was = getattr(enc, "trie_in_eval", True)
@@ -541,7 +594,7 @@ class Generator(nn.Module):
             # launches per trie level, three times slower at C2 where one pass over all rows is wanted
             enc.trie_in_eval = False
             with torch.no_grad():
-                return self._score_rows(data, given)
+                yield
         finally:
             enc.trie_in_eval = trie_was
             for m, was in modes:
@@ -605,18 +658,35 @@ class Generator(nn.Module):
         penalty of that row, by the kernel the searches use (gtos_coverage_step on a zero coverage).  A node whose coverage stays
         near 0 was never verbalised.  Eval mode under no_grad, the module's mode left as found.  Returns ``Coverage``."""
         given = None if targets is None else self._score_sequences(data, targets)
-        modes = [(m, m.training) for m in self.modules()]
-        enc = self.relation_encoder
-        trie_was = getattr(enc, "trie_in_eval", True)
-        try:
-            self.eval()
-            enc.trie_in_eval = False                    # as score_rows: the whole bank in one packed pass
-            with torch.no_grad():
-                return self._coverage(data, given)
-        finally:
-            enc.trie_in_eval = trie_was
-            for m, was in modes:
-                m.training = was
+        with self._as_scorer():
+            return self._coverage(data, given)
+
+    def explain(self, data, targets=None):
+        """Token-level attribution, next to ``score`` and with its target handling: for every target position, whether the token was
+        copied from the graph or generated from the vocabulary, from which node, how sure the model was and how many outputs it
+        preferred (``Explained``).  A post-pass over finished strings -- the batch's own sentences, or the output of any search -- by
+        ONE kernel (gtos_copy_explain_fwd) on the operands of the teacher-forced pass; the [T,N,V+copies] row is never built.  Eval
+        mode under no_grad, the module's mode left as found; no seed is drawn and the host reads nothing (``Explained.rows`` does)."""
+        given = None if targets is None else self._score_sequences(data, targets)
+        with self._as_scorer():
+            out = self._explain(data, given)
+        out.vocab, out.concept_vocab = self.vocabs['predictable_token'], self.vocabs['concept']
+        return out
+
+    def _explain(self, data, given):
+        dev = data['concept'].device
+        if given is not None and not given[0]:          # every n-best list empty: nothing to launch
+            z = lambda dt: torch.zeros((0, 0), dtype=dt, device=dev)        # noqa: E731
+            out = Explained(*[z(d) for _, d in ops.EXPLAIN_OUTPUTS], tokens=torch.zeros(0, dtype=torch.int32, device=dev),
+                            graph_of=torch.zeros(0, dtype=torch.int64, device=dev))
+            out.target = z(torch.int64)
+            return out
+        probe, concept_repr, token_repr, concept_mask, token_mask, attn_mask, cp_seq, target, graph_of = self._teacher_forced(data, given)
+        nll, *rest = self.decoder.explain(probe, concept_repr, token_repr, concept_mask, token_mask, attn_mask, cp_seq, target)
+        live = target.ne(self.vocabs['predictable_token'].padding_idx)
+        out = Explained(-nll, *rest, tokens=live.sum(0).to(torch.int32), graph_of=graph_of)
+        out.target = target
+        return out
 
     def _coverage(self, data, given):
         dev = data['concept'].device

@@ -1300,6 +1300,42 @@ def copy_eval(logits, div, align, cp_seq, target, pad_idx, out=None):
     return nll, pred, p_pred
 
 
+EXPLAIN_OUTPUTS = (("nll", torch.float32), ("entropy", torch.float32), ("gate", torch.float32), ("copy_share", torch.float32),
+                   ("source", torch.int32), ("source_weight", torch.float32), ("focus", torch.int32), ("focus_weight", torch.float32),
+                   ("rank", torch.int32))
+
+
+def copy_explain(logits, div, align, cp_seq, target, pad_idx, out=None):
+    """Token-level attribution of the generate/copy mixture (gtos_copy_explain_fwd, no autograd), operands as ``copy_eval``.  Per row
+    (t, b), nine [T,B] tensors in the order of EXPLAIN_OUTPUTS: nll (bitwise copy_eval's), entropy of the mixture over the vocabulary
+    and the graph's copy ids (nats), gate (the copy gate), copy_share (the part of the target's probability that was copied), source /
+    source_weight (the heaviest position among those that hold the target; -1 / 0 without one), focus / focus_weight (the heaviest
+    position of the row) and rank (how many columns the mixture puts strictly above the target; -1 for a target it cannot produce).
+    source, focus and rank are int32, the rest fp32.  ``out``: the nine tensors to write into."""
+    require_cuda(logits, div, align, cp_seq, target)
+    T_, B, V = logits.shape
+    S = cp_seq.shape[0]
+    logits, div = logits.contiguous(), div.contiguous()
+    align = align.float().contiguous()
+    cp_seq, target = cp_seq.contiguous(), target.contiguous()
+    if cp_seq.dtype != torch.int64 or target.dtype != torch.int64 or tuple(target.shape) != (T_, B):
+        raise _lib.GtosHipError("copy_explain: cp_seq [S,B] and target [T,B] are int64")
+    if out is None:
+        out = tuple(torch.empty((T_, B), dtype=d, device=logits.device) for _, d in EXPLAIN_OUTPUTS)
+    else:
+        out = tuple(out)
+        if len(out) != len(EXPLAIN_OUTPUTS):
+            raise _lib.GtosHipError("copy_explain: out holds %d tensors, one per output: %s"
+                                    % (len(EXPLAIN_OUTPUTS), ", ".join(n for n, _ in EXPLAIN_OUTPUTS)))
+        require_cuda(*out)
+        for t, (name, d) in zip(out, EXPLAIN_OUTPUTS):
+            if t.dtype != d or tuple(t.shape) != (T_, B) or not t.is_contiguous():
+                raise _lib.GtosHipError("copy_explain: out[%s] is a contiguous [T,B] tensor of %s" % (name, d))
+    call("gtos_copy_explain_fwd", dt(logits), T_, B, V, S, ptr(logits), V, ptr(div), ptr(align), ptr(cp_seq), ptr(target),
+         int(pad_idx), *[ptr(t) for t in out], stream())
+    return out
+
+
 def eval_accumulate(nll, pred, target, pad_idx, totals):
     """gtos_eval_accumulate: folds one batch's copy_eval result into the running ``totals`` fp64 [5] = (sum nll, tokens, correct,
     sentences, sum over sentences of nll / tokens) on the device, in a fixed order, and returns the batch's per-sentence

@@ -428,6 +428,25 @@ int gtos_copy_eval_fwd(int dtype, int T, int B, int V, int S, const void* logits
 int gtos_eval_accumulate(int T, int B, const float* nll, const int* pred, const int64_t* target, int64_t pad_idx,
                          double* sent_nll, int* sent_tokens, int* sent_correct, double* totals, void* stream);
 
+/* ---- Token-level attribution (ABI 34; csrc/copy_explain.hip, the rule in csrc/copy_explain_kernels.h): per teacher-forced row, where
+ * the target's probability came from and how sure the model was, again without the ll row.  Operands, SHAPES and error codes as
+ * gtos_copy_eval_fwd; one 256-thread workgroup per row, three passes over its logits, every reduction in a fixed order (two launches
+ * give the same bits).  With q_k = gen_gate * softmax(logits)_k [k < V], p_k = q_k + copy_gate * sum_{s: cp_seq[s,b] == k} align[t,b,s]
+ * and the row's UNIVERSE = the columns [0, V) plus the distinct non-negative copy ids of graph b, all outputs [T,B]:
+ *   nll fp32            bitwise gtos_copy_eval_fwd's
+ *   entropy fp32        -sum_k p_k ln p_k over the universe (nats)
+ *   gate fp32           copy_gate
+ *   copy_share fp32     copy_gate * mass_target / p_target (0 where p_target is 0; exactly 1 for a copy id >= V with positive mass)
+ *   source int32        the position with the largest align among those whose copy id is the target, lowest among equals; -1: none
+ *   source_weight fp32  its align (0 at source == -1)
+ *   focus int32         argmax_s align[t,b,s], lowest among equals, and focus_weight fp32 its value (-1 and 0 at S == 0)
+ *   rank int32          the number of universe columns k != target with p_k > p_target (strict); -1 for a target outside the universe
+ * A padded row (target == pad_idx) gets nll 0, copy_share 0, source -1, source_weight 0, rank -1 and still the other four. */
+int gtos_copy_explain_fwd(int dtype, int T, int B, int V, int S, const void* logits, int64_t ld_logits, const void* div,
+                          const float* align, const int64_t* cp_seq, const int64_t* target, int64_t pad_idx, float* nll,
+                          float* entropy, float* gate, float* copy_share, int* source, float* source_weight, int* focus,
+                          float* focus_weight, int* rank, void* stream);
+
 /* ---- Device-resident beam search (csrc/beam.hip; selection rule in csrc/beam_kernels.h), driven by
  * gtos_amd.search.beam_search_device: generator/search.py's Beam.update / Beam.completed / search_by_batch without a host round trip
  * per step.  B sentences x k fixed hypothesis slots, N = B*k, slot s belongs to sentence s / k; the slots, the token classes, the
