@@ -1724,3 +1724,50 @@ def avoid_block(t, k, ll, parent, token, pat, init, last, n_pos, state_prev, sta
         assert x is None or x.is_contiguous()
     call("gtos_avoid_block", N, k, t, tot, ptr(ll), max(ll.stride(0), tot), ptr(parent) if t else None, ptr(token) if t else None,
          ptr(pat), ptr(init), ptr(last), ptr(n_pos), ptr(state_prev), ptr(state_cur), ptr(active), stream())
+
+
+# ---------------------------------------------------------------------------------------------- clipped n-gram overlap
+# (csrc/overlap.hip; gtos_amd.metrics builds BLEU and chrF++ on it)
+OVERLAP_MAX_SYMBOLS = 4096   # MAX_SYMBOLS of csrc/overlap_kernels.h: the longest row the kernel stages
+OVERLAP_MAX_ORDER = 8        # MAX_ORDER of csrc/overlap_kernels.h
+
+
+def ngram_overlap(sym, off, pairs, n_max):
+    """Clipped n-gram matches of sequence pairs (gtos_ngram_overlap): ``sym`` int32 [off[R]] on the GPU holds R rows of symbols back
+    to back, ``off`` int32 [R+1] their offsets, ``pairs`` int32 [P,2] (hypothesis row, reference row).  ``off`` and ``pairs`` are HOST
+    tensors -- which sequences there are and which of them meet is decided on the host, from strings -- so every check below is
+    made without a device read, before anything is launched; the op uploads them.  Returns int32 [P, n_max, 3] on ``sym``'s device:
+    per order 1 .. n_max the matches, the hypothesis n-grams and the reference n-grams."""
+    require_cuda(sym)
+    if off.is_cuda or pairs.is_cuda:
+        raise _lib.GtosHipError("ngram_overlap: off and pairs are host tensors (the launch is checked on them without a device read)")
+    if not isinstance(n_max, int) or not 1 <= n_max <= OVERLAP_MAX_ORDER:
+        raise _lib.GtosHipError("ngram_overlap: n_max must be an integer in 1..%d, got %r" % (OVERLAP_MAX_ORDER, n_max))
+    if sym.dtype != torch.int32 or sym.dim() != 1 or not sym.is_contiguous():
+        raise _lib.GtosHipError("ngram_overlap: sym must be a contiguous 1-D int32 tensor")
+    if off.dtype != torch.int32 or off.dim() != 1 or off.numel() < 1 or pairs.dtype != torch.int32 or pairs.dim() != 2 \
+            or pairs.shape[1] != 2:
+        raise _lib.GtosHipError("ngram_overlap: off must be int32 [R+1] and pairs int32 [P,2]")
+    off, pairs = off.contiguous(), pairs.contiguous()
+    R, P = off.numel() - 1, pairs.shape[0]
+    if int(off[0]) < 0 or int(off[-1]) != sym.numel():
+        raise _lib.GtosHipError("ngram_overlap: off must start at >= 0 and end at the number of symbols (%d), got %d .. %d"
+                                % (sym.numel(), int(off[0]), int(off[-1])))
+    if R:
+        lens = off[1:] - off[:-1]
+        if int(lens.min()) < 0 or int(lens.max()) > OVERLAP_MAX_SYMBOLS:
+            raise _lib.GtosHipError("ngram_overlap: rows hold 0..%d symbols, got lengths %d..%d"
+                                    % (OVERLAP_MAX_SYMBOLS, int(lens.min()), int(lens.max())))
+    if P and (int(pairs.min()) < 0 or int(pairs.max()) >= R):
+        raise _lib.GtosHipError("ngram_overlap: pair indices must lie in [0, %d), got %d..%d" % (R, int(pairs.min()), int(pairs.max())))
+    out = torch.empty((P, n_max, 3), dtype=torch.int32, device=sym.device)
+    ngram_overlap_into(sym, off, pairs, n_max, out)
+    return out
+
+
+def ngram_overlap_into(sym, off, pairs, n_max, out):
+    """``ngram_overlap`` into a given int32 [P, n_max, 3] device tensor, with no check of its own beyond the entry point's."""
+    P = pairs.shape[0]
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == P * n_max * 3 and out.device == sym.device
+    off_d, pairs_d = off.to(sym.device), pairs.to(sym.device)
+    call("gtos_ngram_overlap", ptr(sym), ptr(off_d), off.numel() - 1, ptr(pairs_d), P, n_max, ptr(off), ptr(pairs), ptr(out), stream())

@@ -237,6 +237,65 @@ class Trainer:
             dist.all_reduce(totals, op=dist.ReduceOp.SUM)       # the one collective of an evaluation
         return eval_metrics(totals.tolist())                    # ... and its one host read
 
+    def validate(self, batches, references=None, beam_size=8, alpha=0.6, max_time_step=100, min_time_step=1, search="device",
+                 return_outputs=False, **work_options):
+        """Held-out validation by decoding, the reference's checkpoint-selection step (generator/work.py ``validate``): per batch
+        ``model.work(batch, beam_size, max_time_step, min_time_step, search, **work_options)``, the best hypothesis of every graph by
+        ``get_k_best(1, alpha)`` without <STR> / <END>, and three gtos_ngram_overlap launches (gtos_amd.metrics: word order 4 for
+        BLEU, punctuation-separated word order 2 and character order 6 for chrF++) accumulated into one device buffer of fp64
+        totals (metrics.N_TOTALS: the summed counts, which are integers and exact, the two lengths, the sentence count and the sum
+        of the sentence chrF++).  Data parallel, each rank passes its own shard of batches and the totals are summed by one
+        all-reduce; then ONE host read, beyond those the searches make.  Returns ``metrics.validation_metrics``: bleu,
+        bleu_precisions, brevity_penalty, chrf (corpus chrF++), chrf_avg (mean sentence chrF++), hyp_tokens, ref_tokens, sentences --
+        and with ``return_outputs`` also ``outputs``, the hypotheses as token-string lists in batch order.
+        ``references``: per batch, one token-string list per graph.  None: they are rebuilt from ``batch['token_out']`` through the
+        predictable-token vocabulary and the graph's ``local_idx2token`` (the ids ride to the host on an asynchronous copy queued
+        in front of the search, whose own reads complete it); a word that was neither in the vocabulary nor copyable is <UNK> there,
+        and an <UNK> matches nothing -- each one is a word and a character of its own -- so such a validation scores a little below
+        one on the true strings.  What is scored are the preprocessed token strings as given: no lowercasing, no de-anonymising
+        post-processing.
+        The training state is left alone, as for ``evaluate``: parameters, bf16 mirror, gradient bucket, Adam moments, counters and
+        the model's train / eval mode.  A ``search`` that draws a seed ("sample", "stochastic") without ``seed=`` moves the seed
+        counter exactly as ``work`` moves it, once per batch; pass ``seed`` for a repeatable validation."""
+        from . import metrics
+        from .vocab import END, PAD
+        dev = self.flat.param.device
+        totals = torch.zeros(metrics.N_TOTALS, dtype=torch.float64, device=dev)
+        vocab = self.model.vocabs['predictable_token']
+        outputs = []
+        modes = [(m, m.training) for m in self.model.modules()]
+        try:
+            self.model.eval()
+            for i, batch in enumerate(batches):
+                ids = done = None
+                if references is None:
+                    ids, done = _ids_to_host(batch['token_out'])
+                beams = self.model.work(batch, beam_size, max_time_step, min_time_step, search, **work_options)
+                hyps = [metrics.hypothesis_tokens(best[0]) if best else [] for best in (beam.get_k_best(1, alpha) for beam in beams)]
+                if references is None:
+                    if done is not None:
+                        done.synchronize()          # long complete: work() has read the device since
+                    refs = []
+                    for b, local in enumerate(batch['local_idx2token']):
+                        words = [local[y] if y in local else vocab.idx2token(y) for y in ids[:, b].tolist()]
+                        refs.append([w for w in words if w not in (END, PAD)])
+                else:
+                    refs = [list(r) for r in references[i]]
+                if len(refs) != len(hyps):
+                    raise ValueError("references[%d] holds one token-string list per graph: %d graphs, got %d" % (i, len(hyps), len(refs)))
+                if hyps:
+                    metrics.accumulate(totals, *(metrics.overlap(hyps, refs, None, kind, device=dev) for kind in ("word", "chrf_word", "char")))
+                outputs += hyps
+        finally:
+            for m, was in modes:
+                m.training = was
+        if self.world_size > 1:
+            dist.all_reduce(totals, op=dist.ReduceOp.SUM)       # the one collective of a validation
+        out = metrics.validation_metrics(totals.tolist())       # ... and its one host read
+        if return_outputs:
+            out["outputs"] = outputs
+        return out
+
 
 def eval_metrics(totals):
     """The dict of Trainer.evaluate from the five totals of gtos_eval_accumulate (sum nll, tokens, correct, sentences, sum over
@@ -247,6 +306,18 @@ def eval_metrics(totals):
     return {"nll_per_token": per_token, "perplexity": math.exp(min(per_token, 700.0)) if n else float("nan"),
             "accuracy": ok / n if n else float("nan"), "tokens": int(n), "sentences": int(sents),
             "loss": norm / sents if sents else float("nan")}
+
+
+def _ids_to_host(t):
+    """(host copy of the id tensor ``t``, the event that completes it or None): a device tensor is copied asynchronously into pinned
+    memory on the current stream -- the host does not wait here."""
+    if not t.is_cuda:
+        return t, None
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    return host, done
 
 
 class GraphedStep:

@@ -695,6 +695,21 @@ int gtos_truncate_block(int N, int k, int t, int V, int tot, int min_time_step, 
                         const uint8_t* flag_local, const uint8_t* owned_local, const int* slot_state, const int* active,
                         void* stream);
 
+/* ---- Clipped n-gram overlap of sequence pairs (ABI 35; csrc/overlap.hip, the rule in csrc/overlap_kernels.h), driven by
+ * gtos_amd.metrics: the exact count behind BLEU (word ids, order 4) and both halves of chrF++ (word ids after punctuation
+ * separation, order 2; code points, order 6) -- what generator/work.py's validate gets from multi-bleu.perl and chrF++.py.
+ * R sequences of int32 symbols in CSR form: sym [off[R]] and off int32 [R+1], ascending from off[0] >= 0; a row may be empty.
+ * pairs int32 [P,2] = (hypothesis row, reference row); any list, rows and pairs may repeat.  One 256-thread workgroup per pair writes
+ *   out int32 [P, n_max, 3] = per order n = 1 .. n_max: matches, hypothesis n-grams max(Lh - n + 1, 0), reference n-grams
+ *   max(Lr - n + 1, 0); matches = sum over the distinct n-grams g of min(count_h(g), count_r(g)), computed without hashing (exact).
+ * sym, off, pairs and out are device pointers.  off_host and pairs_host are HOST copies of off and pairs, read by the entry point
+ *   only, to check the launch before it is made: the list of sequences and pairs comes from the host (strings), so no device read
+ *   is needed.  A device copy that disagrees with its host copy stores nothing for the pairs it makes invalid.
+ *   SHAPES (-10 outside, nothing launched): 1 <= n_max <= 8, every row at most 4096 symbols (both rows of a pair are staged in LDS),
+ *   every pair index in [0, R), no null pointer (sym may be null when there are no symbols).  P == 0: success, no launch. */
+int gtos_ngram_overlap(const int* sym, const int* off, int R, const int* pairs, int P, int n_max, const int* off_host,
+                       const int* pairs_host, int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
