@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgtos_hip.so")
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 c_p, c_i, c_l, c_f, c_u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64
 
@@ -77,6 +77,7 @@ SIGNATURES = {
     "gtos_ngram_block": [c_i] * 6 + [c_p, c_l] + [c_p] * 6,
     "gtos_avoid_block": [c_i] * 4 + [c_p, c_l] + [c_p] * 10,
     "gtos_ngram_overlap": [c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
+    "gtos_ngram_overlap_groups": [c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     "gtos_truncate_block": [c_i] * 6 + [c_f] * 5 + [c_p, c_l] + [c_p] * 6,
     "gtos_diverse_advance": [c_i] * 3 + [c_u64] + [c_i] * 5 + [c_p] * 13,
     "gtos_diverse_reorder": [c_i, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_l, c_p,

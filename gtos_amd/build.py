@@ -5,7 +5,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libgtos_hip.so")
-SOURCES = ["gemm.hip", "rel_attn.hip", "attn_tile.hip", "rowops.hip", "gru_step.hip", "copy_nll.hip", "tokenenc.hip", "pathtrie_dev.hip", "relbatch_dev.hip", "relindex_dev.hip", "beam.hip", "sample.hip", "copy_ls.hip", "copy_eval.hip", "copy_explain.hip", "ngram.hip", "diverse.hip", "constrain.hip", "coverage.hip", "phrase.hip", "avoid.hip", "sbs.hip", "truncate.hip", "overlap.hip"]
+SOURCES = ["gemm.hip", "rel_attn.hip", "attn_tile.hip", "rowops.hip", "gru_step.hip", "copy_nll.hip", "tokenenc.hip", "pathtrie_dev.hip", "relbatch_dev.hip", "relindex_dev.hip", "beam.hip", "sample.hip", "copy_ls.hip", "copy_eval.hip", "copy_explain.hip", "ngram.hip", "diverse.hip", "constrain.hip", "coverage.hip", "phrase.hip", "avoid.hip", "sbs.hip", "truncate.hip", "overlap.hip", "mbr.hip"]
 EXACT_FP = {"relbatch_dev.hip", "beam.hip", "sample.hip", "diverse.hip", "constrain.hip", "coverage.hip", "phrase.hip", "sbs.hip", "truncate.hip"}      # double comparisons / sums that must come out like the host code: no fast-math, no contraction
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffast-math", "-fno-finite-math-only"]
@@ -59,6 +59,7 @@ def build(force=False, verbose=True):
                "ngram.hip": "common.h ngram_kernels.h slot_kernels.h",
                "avoid.hip": "common.h avoid_kernels.h slot_kernels.h",
                "overlap.hip": "common.h overlap_kernels.h slot_kernels.h",
+               "mbr.hip": "common.h mbr_kernels.h overlap_kernels.h slot_kernels.h",
                "truncate.hip": "truncate_kernels.h sample_kernels.h slot_kernels.h slot_device.h common.h",
                "diverse.hip": "diverse_kernels.h beam_kernels.h beam_device.h slot_kernels.h slot_device.h reorder_device.h",
                "constrain.hip": "constrain_kernels.h beam_kernels.h beam_device.h slot_kernels.h slot_device.h common.h",

@@ -1241,6 +1241,6 @@ extern "C" int gtos_set_seed_epoch(const void* epoch) {
     return rc;
 }
 
-extern "C" int gtos_abi_version(void) { return 35; }
+extern "C" int gtos_abi_version(void) { return 36; }
 
 GTOS_SEED_EPOCH_SETTER(rowops)

@@ -15,8 +15,15 @@ torch operations on those counts that never read the host: they take host or dev
 live.  Scores are on the 0..100 scale the two programs print.  ``best_of_nbest`` picks, per graph, the hypothesis of an n-best list
 that scores best against the reference; ``Trainer.validate`` (gtos_amd.train) is the checkpoint-selection step itself.
 
+Without a reference, ``mbr_select`` picks by minimum Bayes risk: the candidate of a sample set or n-best list with the highest
+expected sentence chrF++ against the set itself, each member weighted by how probable it is.  ``pairwise`` counts all ordered pairs
+inside every graph's candidate group in one launch (ops.ngram_overlap_groups -> gtos_ngram_overlap_groups, csrc/mbr_kernels.h: one
+workgroup per candidate, half of the group scanned, no pair list) and ``expected_utility`` is the fp64 weighting and the per-group
+argmax, again without a host read.
+
 One reference per hypothesis; the tokens are scored as given (no lowercasing, no tokeniser of its own).
 """
+import math
 import string
 
 import torch
@@ -58,6 +65,7 @@ def encode(sentences, kind, unknown=UNK):
         raise ValueError("kind must be one of %s, got %r" % (sorted(KINDS), kind))
     table, sym, off = {}, [], [0]
     fresh = -1                                   # ids of unknown words: negative, never equal to a table id or a code point
+    seen = {}                                    # token string -> its symbols (the candidates of a sample set repeat their words)
     for words in sentences:
         if isinstance(words, str) or not all(isinstance(w, str) for w in words):
             raise ValueError("a sentence is a list of token strings, got %r" % (words,))
@@ -65,10 +73,15 @@ def encode(sentences, kind, unknown=UNK):
             if unknown is not None and w == unknown:
                 sym.append(fresh)
                 fresh -= 1
-            elif kind == "char":
-                sym.extend(ord(c) for c in w if c != " ")
-            else:
-                sym.extend(table.setdefault(x, len(table)) for x in (separate_punctuation([w]) if kind == "chrf_word" else [w]))
+                continue
+            s = seen.get(w)
+            if s is None:
+                if kind == "char":
+                    s = [ord(c) for c in w if c != " "]
+                else:
+                    s = [table.setdefault(x, len(table)) for x in (separate_punctuation([w]) if kind == "chrf_word" else [w])]
+                seen[w] = s
+            sym.extend(s)
         off.append(len(sym))
     return torch.tensor(sym, dtype=torch.int32), torch.tensor(off, dtype=torch.int32)
 
@@ -190,6 +203,129 @@ def best_of_nbest(beams, references, k=None, alpha=0.6, beta=2.0, device="cuda")
     for b, (i, s) in enumerate(zip(*picked)):
         out.append((lists[b][int(i)], int(i), s) if lists[b] else (None, -1, float("nan")))
     return out
+
+
+def pairwise(groups, kind, n_max=None, device="cuda"):
+    """All ordered (hypothesis, reference) pairs inside every group: ``groups`` is a list of G lists of token-string lists (the
+    candidates of G graphs; a group may be empty).  Returns ``(stats, cell_off)``: the device statistics int32 [cells, n_max, 3],
+    cells = sum n_g^2, and the host tensor cell_off int64 [G+1], the running sum of n_g^2 -- the cell of (candidate i as
+    hypothesis, candidate j as reference) of group g is ``cell_off[g] + i * n_g + j`` and holds what ``overlap`` gives for that
+    pair.  One ``encode`` call for everything (ids are comparable across the batch) and ONE gtos_ngram_overlap_groups launch; the
+    host reads nothing.  A batch in which some group holds more than ops.OVERLAP_MAX_GROUP candidates or some row more than
+    ops.OVERLAP_GROUP_MAX_SYMBOLS symbols goes through ops.ngram_overlap on the explicit ordered pair list instead (rows up to
+    ops.OVERLAP_MAX_SYMBOLS symbols stay legal there), into the same layout.  The limits alone decide the route: inside them the
+    grouped kernel measured faster at every shape, 1.2x at 8 candidates per group to 3.1x at 64 (tools/bench_mbr.py)."""
+    n_max = KINDS[kind] if n_max is None else n_max
+    groups = [[list(c) for c in g] for g in groups]
+    sizes = [len(g) for g in groups]
+    sym, off = encode([c for g in groups for c in g], kind)
+    grp = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0).to(torch.int32)
+    cell_off = ops.group_cell_offsets(grp)
+    longest = int((off[1:] - off[:-1]).max()) if off.numel() > 1 else 0
+    if max(sizes, default=0) <= ops.OVERLAP_MAX_GROUP and longest <= ops.OVERLAP_GROUP_MAX_SYMBOLS \
+            and int(cell_off[-1]) * n_max * 3 <= ops.OVERLAP_GROUP_MAX_OUT:
+        return ops.ngram_overlap_groups(sym.to(device), off, grp, n_max), cell_off
+    pairs = torch.cat([torch.stack([a.repeat_interleave(n), a.repeat(n)], 1)
+                       for a, n in ((torch.arange(s, s + n, dtype=torch.int32), n) for s, n in zip(grp.tolist(), sizes))]
+                      or [torch.zeros((0, 2), dtype=torch.int32)])
+    return ops.ngram_overlap(sym.to(device), off, pairs, n_max), cell_off
+
+
+def expected_utility(stats_char6, stats_word2, sizes, weights=None, beta=2.0):
+    """Minimum-Bayes-risk values from ``pairwise``'s statistics of the same groups ("char" at order 6, "chrf_word" at order 2;
+    ``sizes`` = the host list of the G group sizes n_g, R = their sum).  With U[i, j] the sentence chrF++ of candidate i as
+    hypothesis against candidate j as reference, the value of candidate i is sum_j w_j U[i, j] / sum_j w_j over its own group, j = i
+    included.  ``weights``: None (uniform: the Monte-Carlo estimate for independent samples) or one non-negative fp64 value per
+    candidate, in row order (a list, a host or a device tensor); a candidate of weight 0 is still a candidate but no evidence, and a
+    group whose weights sum to 0 is treated as uniform.  A few fp64 torch operations where the statistics live, in a fixed order
+    (identical candidates get identical values); nothing reads the host.  Returns ``(value fp64 [R], index int64 [G])``: the first
+    maximum of every group, counted inside the group, -1 for an empty group."""
+    sizes = [int(n) for n in sizes]
+    U = sentence_chrf(stats_char6, stats_word2, beta)
+    dev = U.device
+    G, R, m = len(sizes), sum(sizes), max(sizes, default=0)
+    if U.numel() != sum(n * n for n in sizes):
+        raise ValueError("expected_utility: %d cells for groups of sizes %s" % (U.numel(), sizes))
+    if weights is not None:
+        weights = torch.as_tensor(weights, dtype=torch.float64).reshape(-1)
+        if weights.numel() != R:
+            raise ValueError("expected_utility: one weight per candidate: %d candidates, %d weights" % (R, weights.numel()))
+    if R == 0:
+        return torch.zeros(0, dtype=torch.float64, device=dev), torch.full((G,), -1, dtype=torch.int64, device=dev)
+    # index tensors built on the host from the sizes alone
+    group_of = torch.repeat_interleave(torch.arange(G, dtype=torch.int64), torch.tensor(sizes, dtype=torch.int64))
+    start = torch.tensor([0] + sizes[:-1], dtype=torch.int64).cumsum(0)
+    within = torch.arange(R, dtype=torch.int64) - start[group_of]
+    n_of = torch.tensor(sizes, dtype=torch.int64)[group_of]
+    cell_g = torch.repeat_interleave(group_of, n_of)                                   # [cells]: row-major inside a group
+    cell_i = torch.repeat_interleave(within, n_of)
+    cell_start = (torch.cumsum(n_of, 0) - n_of)
+    cell_j = torch.arange(U.numel(), dtype=torch.int64) - torch.repeat_interleave(cell_start, n_of)
+    group_of, within, cell_g, cell_i, cell_j = (t.to(dev) for t in (group_of, within, cell_g, cell_i, cell_j))
+    grid = torch.zeros((G, m, m), dtype=torch.float64, device=dev)
+    grid[cell_g, cell_i, cell_j] = U
+    valid = torch.zeros((G, m), dtype=torch.bool, device=dev)
+    valid[group_of, within] = True
+    w = valid.to(torch.float64)
+    if weights is not None:
+        given = torch.zeros((G, m), dtype=torch.float64, device=dev)
+        given[group_of, within] = weights.to(dev)
+        w = torch.where(given.sum(1, keepdim=True) > 0, given, w)
+    total = w.sum(1, keepdim=True)
+    value = (grid * w[:, None, :]).sum(2) / torch.where(total > 0, total, torch.ones_like(total))
+    masked = torch.where(valid, value, torch.full_like(value, -1.0))                   # (chrF++ is never negative)
+    top = masked.max(1, keepdim=True).values
+    column = torch.arange(m, dtype=torch.int64, device=dev).expand(G, m)
+    index = torch.where(valid & (masked == top), column, torch.full_like(column, m)).min(1).values
+    index = torch.where(index < m, index, torch.full_like(index, -1))
+    return value[group_of, within], index
+
+
+def mbr_candidates(beams, k=None, alpha=0.6, weights="uniform", scale=1.0):
+    """The candidates ``mbr_select`` weighs, per beam, and their weights: (groups, per-group weight lists or None for uniform)."""
+    if weights not in ("uniform", "score", "stochastic"):
+        raise ValueError("weights must be 'uniform', 'score' or 'stochastic', got %r" % (weights,))
+    groups, w = [], []
+    for beam in beams:
+        if weights == "stochastic":
+            from .search import stochastic_weights
+            pairs = stochastic_weights(beam)[0]
+            groups.append([hypothesis_tokens(h) for h, _ in pairs])
+            w.append([float(x) for _, x in pairs])
+            continue
+        best = beam.get_k_best(beam.beam_size if k is None else k, alpha)
+        groups.append([hypothesis_tokens(h) for h in best])
+        w.append([])
+        if weights == "score" and best:
+            top = max(scale * h.score for h in best)
+            e = [math.exp(scale * h.score - top) for h in best]
+            w[-1] = [x / sum(e) for x in e]
+    return groups, (None if weights == "uniform" else w)
+
+
+def mbr_select(beams, k=None, alpha=0.6, weights="uniform", scale=1.0, beta=2.0, device="cuda"):
+    """Per graph, the minimum-Bayes-risk choice among its candidates: the one with the highest expected sentence chrF++ against the
+    candidates themselves (``expected_utility``); among equals the first.  The sibling of ``best_of_nbest`` for when there is no
+    reference.  Candidates: ``beam.get_k_best(k, alpha)`` in that order (``k`` None: the beam's width) without <STR> / <END>;
+    with ``weights="stochastic"`` the hypotheses ``search.stochastic_weights(beam)`` returns, in its order.  ``weights``:
+      "uniform"     every candidate counts once -- the Monte-Carlo estimate for independent samples (search="sample"): a sentence
+                    drawn twice is in the list twice and counts twice;
+      "score"       w proportional to exp(scale * h.score), normalised per graph with the maximum subtracted, in fp64: for n-best lists;
+      "stochastic"  the importance weights of a stochastic beam search (search="stochastic").
+    Two ``pairwise`` launches for the whole batch (character order 6, chrF++ words order 2) and ONE host read.  Returns one
+    (tokens, index, expected utility) per graph; (None, -1, nan) for a beam without candidates."""
+    groups, per_group = mbr_candidates(beams, k, alpha, weights, scale)
+    w = None if per_group is None else [x for ws in per_group for x in ws]
+    sizes = [len(g) for g in groups]
+    if not sum(sizes):
+        return [(None, -1, float("nan")) for _ in beams]
+    char, _ = pairwise(groups, "char", device=device)
+    word, _ = pairwise(groups, "chrf_word", device=device)
+    value, index = expected_utility(char, word, sizes, w, beta)
+    first = torch.tensor([0] + sizes[:-1], dtype=torch.int64).cumsum(0).to(value.device)
+    chosen = value[(first + index.clamp(min=0)).clamp(max=value.numel() - 1)]
+    picked = torch.stack([index.to(torch.float64), chosen]).tolist()                # the one host read
+    return [(groups[b][int(i)], int(i), u) if sizes[b] else (None, -1, float("nan")) for b, (i, u) in enumerate(zip(*picked))]
 
 
 def accumulate(totals, stats_word4, stats_chrf_word2, stats_char6, beta=2.0):

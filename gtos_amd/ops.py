@@ -1771,3 +1771,71 @@ def ngram_overlap_into(sym, off, pairs, n_max, out):
     assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == P * n_max * 3 and out.device == sym.device
     off_d, pairs_d = off.to(sym.device), pairs.to(sym.device)
     call("gtos_ngram_overlap", ptr(sym), ptr(off_d), off.numel() - 1, ptr(pairs_d), P, n_max, ptr(off), ptr(pairs), ptr(out), stream())
+
+
+# ---------------------------------------------------------------------------------------------- all pairs inside groups
+# (csrc/mbr.hip; gtos_amd.metrics.pairwise and mbr_select build minimum-Bayes-risk selection on it)
+OVERLAP_MAX_GROUP = 64              # MAX_GROUP of csrc/mbr_kernels.h: the candidates of a group
+OVERLAP_GROUP_MAX_SYMBOLS = 1024    # GROUP_MAX_SYMBOLS of csrc/mbr_kernels.h: the longest row of a grouped launch
+OVERLAP_GROUP_MAX_OUT = 2 ** 31 - 1   # MAX_OUT of csrc/mbr_kernels.h: the integers of a grouped launch's output
+
+
+def group_cell_offsets(grp):
+    """cell_off int64 [G+1] of a host grp int32 [G+1]: the running sum of n_g^2 (cell_offsets of csrc/mbr_kernels.h)."""
+    n = (grp[1:] - grp[:-1]).to(torch.int64)
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(n * n, 0)])
+
+
+def ngram_overlap_groups(sym, off, grp, n_max):
+    """Clipped n-gram matches of ALL ordered pairs inside groups of rows (gtos_ngram_overlap_groups): ``sym`` / ``off`` as for
+    ``ngram_overlap``, ``grp`` int32 [G+1] the row offsets of the groups, from 0 to R, non-decreasing (an empty group is legal).
+    ``off`` and ``grp`` are HOST tensors: every check below is made without a device read, before anything is launched; the op
+    uploads them.  Returns int32 [cells, n_max, 3] on ``sym``'s device, cells = sum n_g^2: the cell of (hypothesis i, reference j) of
+    group g is ``group_cell_offsets(grp)[g] + i * n_g + j`` and holds what ``ngram_overlap`` returns for that pair of rows."""
+    require_cuda(sym)
+    if off.is_cuda or grp.is_cuda:
+        raise _lib.GtosHipError("ngram_overlap_groups: off and grp are host tensors (the launch is checked on them without a device read)")
+    if not isinstance(n_max, int) or not 1 <= n_max <= OVERLAP_MAX_ORDER:
+        raise _lib.GtosHipError("ngram_overlap_groups: n_max must be an integer in 1..%d, got %r" % (OVERLAP_MAX_ORDER, n_max))
+    if sym.dtype != torch.int32 or sym.dim() != 1 or not sym.is_contiguous():
+        raise _lib.GtosHipError("ngram_overlap_groups: sym must be a contiguous 1-D int32 tensor")
+    if off.dtype != torch.int32 or off.dim() != 1 or off.numel() < 1 or grp.dtype != torch.int32 or grp.dim() != 1 or grp.numel() < 1:
+        raise _lib.GtosHipError("ngram_overlap_groups: off must be int32 [R+1] and grp int32 [G+1]")
+    off, grp = off.contiguous(), grp.contiguous()
+    R, G = off.numel() - 1, grp.numel() - 1
+    if int(off[0]) < 0 or int(off[-1]) != sym.numel():
+        raise _lib.GtosHipError("ngram_overlap_groups: off must start at >= 0 and end at the number of symbols (%d), got %d .. %d"
+                                % (sym.numel(), int(off[0]), int(off[-1])))
+    if R:
+        lens = off[1:] - off[:-1]
+        if int(lens.min()) < 0 or int(lens.max()) > OVERLAP_GROUP_MAX_SYMBOLS:
+            raise _lib.GtosHipError("ngram_overlap_groups: rows hold 0..%d symbols, got lengths %d..%d"
+                                    % (OVERLAP_GROUP_MAX_SYMBOLS, int(lens.min()), int(lens.max())))
+    if int(grp[0]) != 0 or int(grp[-1]) != R:
+        raise _lib.GtosHipError("ngram_overlap_groups: grp must run from 0 to the number of rows (%d), got %d .. %d"
+                                % (R, int(grp[0]), int(grp[-1])))
+    if G:
+        sizes = grp[1:] - grp[:-1]
+        if int(sizes.min()) < 0 or int(sizes.max()) > OVERLAP_MAX_GROUP:
+            raise _lib.GtosHipError("ngram_overlap_groups: groups hold 0..%d rows, got sizes %d..%d"
+                                    % (OVERLAP_MAX_GROUP, int(sizes.min()), int(sizes.max())))
+    cells = int(group_cell_offsets(grp)[-1])
+    if cells * n_max * 3 > OVERLAP_GROUP_MAX_OUT:
+        raise _lib.GtosHipError("ngram_overlap_groups: the output holds at most %d integers, got %d cells x %d x 3"
+                                % (OVERLAP_GROUP_MAX_OUT, cells, n_max))
+    out = torch.empty((cells, n_max, 3), dtype=torch.int32, device=sym.device)
+    ngram_overlap_groups_into(sym, off, grp, n_max, out)
+    return out
+
+
+def ngram_overlap_groups_into(sym, off, grp, n_max, out):
+    """``ngram_overlap_groups`` into a given int32 [cells, n_max, 3] device tensor, with no check of its own beyond the entry point's
+    (and that of the output's size, on the host copy of grp)."""
+    if off.is_cuda or grp.is_cuda:
+        raise _lib.GtosHipError("ngram_overlap_groups: off and grp are host tensors (the launch is checked on them without a device read)")
+    sizes = (grp[1:] - grp[:-1]).to(torch.int64)
+    cells = int((sizes * sizes).sum())
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == cells * n_max * 3 and out.device == sym.device
+    off_d, grp_d = off.to(sym.device), grp.to(sym.device)
+    call("gtos_ngram_overlap_groups", ptr(sym), ptr(off_d), off.numel() - 1, ptr(grp_d), grp.numel() - 1, n_max, ptr(off), ptr(grp),
+         ptr(out), stream())

@@ -238,7 +238,7 @@ class Trainer:
         return eval_metrics(totals.tolist())                    # ... and its one host read
 
     def validate(self, batches, references=None, beam_size=8, alpha=0.6, max_time_step=100, min_time_step=1, search="device",
-                 return_outputs=False, **work_options):
+                 return_outputs=False, select="best", mbr_weights="uniform", mbr_scale=1.0, **work_options):
         """Held-out validation by decoding, the reference's checkpoint-selection step (generator/work.py ``validate``): per batch
         ``model.work(batch, beam_size, max_time_step, min_time_step, search, **work_options)``, the best hypothesis of every graph by
         ``get_k_best(1, alpha)`` without <STR> / <END>, and three gtos_ngram_overlap launches (gtos_amd.metrics: word order 4 for
@@ -256,13 +256,22 @@ class Trainer:
         post-processing.
         The training state is left alone, as for ``evaluate``: parameters, bf16 mirror, gradient bucket, Adam moments, counters and
         the model's train / eval mode.  A ``search`` that draws a seed ("sample", "stochastic") without ``seed=`` moves the seed
-        counter exactly as ``work`` moves it, once per batch; pass ``seed`` for a repeatable validation."""
+        counter exactly as ``work`` moves it, once per batch; pass ``seed`` for a repeatable validation.
+        ``select``: "best" (above), or "mbr": what is scored per graph is the minimum-Bayes-risk choice among the beam's candidates,
+        ``metrics.mbr_select(beams, beam_size, alpha, mbr_weights, mbr_scale)`` -- the candidate with the highest expected sentence
+        chrF++ against the candidates themselves, weighted "uniform" (independent samples, search="sample"), by "score" (exp(mbr_scale
+        * log-likelihood), n-best lists) or "stochastic" (the importance weights of search="stochastic") -- and ``outputs`` are those
+        choices.  It adds two gtos_ngram_overlap_groups launches per batch, scores every candidate against the reference and lets the
+        device pick the rows of the choices: at most ONE host read more than "best", for all batches, and only with
+        ``return_outputs``.  A graph whose beam offers mbr_select no candidate keeps its ``get_k_best(1, alpha)`` choice.  Any other ``select`` raises ValueError."""
         from . import metrics
+        if select not in ("best", "mbr"):
+            raise ValueError("select must be 'best' or 'mbr', got %r" % (select,))
         from .vocab import END, PAD
         dev = self.flat.param.device
         totals = torch.zeros(metrics.N_TOTALS, dtype=torch.float64, device=dev)
         vocab = self.model.vocabs['predictable_token']
-        outputs = []
+        outputs, chosen = [], []
         modes = [(m, m.training) for m in self.model.modules()]
         try:
             self.model.eval()
@@ -271,7 +280,15 @@ class Trainer:
                 if references is None:
                     ids, done = _ids_to_host(batch['token_out'])
                 beams = self.model.work(batch, beam_size, max_time_step, min_time_step, search, **work_options)
+                if select == "mbr":                         # (before get_k_best below, which may merge a beam's two lists)
+                    groups, weights = metrics.mbr_candidates(beams, beam_size, alpha, mbr_weights, mbr_scale)
                 hyps = [metrics.hypothesis_tokens(best[0]) if best else [] for best in (beam.get_k_best(1, alpha) for beam in beams)]
+                if select == "mbr":
+                    for b, h in enumerate(hyps):
+                        if not groups[b]:                   # no candidate to weigh: the graph keeps its model-score choice
+                            groups[b] = [h]
+                            if weights is not None:
+                                weights[b] = [1.0]
                 if references is None:
                     if done is not None:
                         done.synchronize()          # long complete: work() has read the device since
@@ -283,9 +300,23 @@ class Trainer:
                     refs = [list(r) for r in references[i]]
                 if len(refs) != len(hyps):
                     raise ValueError("references[%d] holds one token-string list per graph: %d graphs, got %d" % (i, len(hyps), len(refs)))
-                if hyps:
+                if hyps and select == "mbr":
+                    # every candidate is scored against its graph's reference and the device picks the rows of the choices: the
+                    # host learns the choices only when it has to return them, in one read for all batches
+                    sizes = [len(g) for g in groups]
+                    _, index = metrics.expected_utility(metrics.pairwise(groups, "char", device=dev)[0],
+                                                        metrics.pairwise(groups, "chrf_word", device=dev)[0], sizes,
+                                                        None if weights is None else [x for ws in weights for x in ws])
+                    rows = torch.tensor([0] + sizes[:-1], dtype=torch.int64).cumsum(0).to(dev) + index
+                    flat = [c for g in groups for c in g]
+                    pairs = [(r, b) for r, b in enumerate(b for b, n in enumerate(sizes) for _ in range(n))]
+                    metrics.accumulate(totals, *(metrics.overlap(flat, refs, pairs, kind, device=dev)[rows]
+                                                 for kind in ("word", "chrf_word", "char")))
+                    chosen.append(index)
+                    outputs += groups
+                elif hyps:
                     metrics.accumulate(totals, *(metrics.overlap(hyps, refs, None, kind, device=dev) for kind in ("word", "chrf_word", "char")))
-                outputs += hyps
+                    outputs += hyps
         finally:
             for m, was in modes:
                 m.training = was
@@ -293,6 +324,8 @@ class Trainer:
             dist.all_reduce(totals, op=dist.ReduceOp.SUM)       # the one collective of a validation
         out = metrics.validation_metrics(totals.tolist())       # ... and its one host read
         if return_outputs:
+            if chosen:                                          # select="mbr": outputs holds the candidate groups
+                outputs = [g[j] for g, j in zip(outputs, torch.cat(chosen).tolist())]     # ... its one host read more
             out["outputs"] = outputs
         return out
 

@@ -710,6 +710,25 @@ int gtos_truncate_block(int N, int k, int t, int V, int tot, int min_time_step, 
 int gtos_ngram_overlap(const int* sym, const int* off, int R, const int* pairs, int P, int n_max, const int* off_host,
                        const int* pairs_host, int* out, void* stream);
 
+/* ---- The same count for ALL ordered pairs inside groups of rows (ABI 36; csrc/mbr.hip, rule and schedule in csrc/mbr_kernels.h),
+ * driven by gtos_amd.metrics.pairwise: the statistic under minimum-Bayes-risk selection, every candidate of a graph against every
+ * other.  sym / off as above; grp int32 [G+1] = non-decreasing row offsets from grp[0] = 0 to grp[G] = R: group g holds the rows
+ * grp[g] .. grp[g+1], n_g of them (0 is legal).
+ *   out int32 [cells, n_max, 3], cells = sum over g of n_g^2: the cell of (hypothesis i, reference j) of group g, i and j counted
+ *   inside the group, is cell_off[g] + i * n_g + j with cell_off the running sum of n_g^2, and holds exactly what gtos_ngram_overlap
+ *   stores for the pair (row grp[g] + i, row grp[g] + j).
+ * One 256-thread workgroup per row (it finds its group from grp): the row is staged once, the part of the rule that looks at the
+ * hypothesis alone is computed once, and as the clipped count is symmetric only half of the group is scanned, each scan storing
+ * the two mirrored cells; the diagonal is stored without a scan.  No pair list, no atomics: two launches store identical values.
+ * sym, off, grp and out are device pointers; off_host and grp_host are HOST copies read by the entry point only, to check the
+ *   launch before it is made.  A device copy that is not a grouping of the same R rows into the same number of cells, or whose
+ *   row offsets leave the limits, stores nothing.
+ *   SHAPES (-10 outside, nothing launched): 1 <= n_max <= 8, grp as above with every group at most 64 rows, every row at most 1024
+ *   symbols, cells * n_max * 3 <= 2^31 - 1, no null pointer (sym may be null when there are no symbols).  G == 0 or R == 0:
+ *   success, no launch. */
+int gtos_ngram_overlap_groups(const int* sym, const int* off, int R, const int* grp, int G, int n_max, const int* off_host,
+                              const int* grp_host, int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
