@@ -415,7 +415,9 @@ __global__ __launch_bounds__(256) void rel_attn_bwd_q_kernel(AttnArgs a) {
             float dp = dpv;
             if (a.dw && act) dp += a.dw[off];
             const float gsc = a.scale * p * (keep * dp - D);
-            if (lead) { a.pd[off] = p * keep; a.gs[off] = gsc; }
+            // the hand-over P~ of a call whose forward returned its weights IS that tensor: dv = w^T d_o and the sum w.dw inside D then
+            // differentiate the very values the caller holds (exp(s - m) / l of the forward and exp(s - lse) here differ in their last bits)
+            if (lead) { a.pd[off] = a.w ? a.w[off] : p * keep; a.gs[off] = gsc; }
             float dra[8], drb[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) { dra[e] = gsc * rb[e]; drb[e] = gsc * ra[e]; dq[e] += dra[e]; }

@@ -77,7 +77,7 @@ int gtos_rel_attn_fwd(int dtype, int mode, int T, int S, int B, int H, int d,
  * mode 2 leaves the bank gradient to gtos_rel_attn_bwd_bank -- except for types whose id carries bit 31 in idx_q / idx_k
  * (set by the host index for types that occur exactly once in the batch): their single pair's term IS their bank gradient
  * row and is written straight into d_rel[type] (row stride ld_drel; d_rel may be NULL when no id is flagged).
- * pd/gs are caller-provided fp32 scratch [T,S,B,H] (post-dropout probabilities, scale*dS).  The MFMA tile path of mode 0 (see
+ * pd/gs are caller-provided fp32 scratch [T,S,B,H] (post-dropout probabilities -- with w given, a copy of w -- and scale*dS).  The MFMA tile path of mode 0 (see
  * gtos_rel_attn_fwd; one launch) keeps both on chip: pd and gs may be NULL for a call it covers, and -15 is returned when a call
  * that needs them comes without. */
 int gtos_rel_attn_bwd(int dtype, int mode, int T, int S, int B, int H, int d,

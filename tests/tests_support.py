@@ -326,3 +326,150 @@ def segment_sum_bounds(v, node_of_row, n_nodes, dtype=torch.bfloat16):
     S = torch.zeros_like(ref).index_add(0, node_of_row, v.abs())
     cnt = torch.bincount(node_of_row, minlength=n_nodes)
     return ref, stored_bound(ref, c_acc_of(cnt)[:, None] * S, dtype)
+
+
+# ------------------------------------------------------------------------------------------------ relation attention: fp64 and bounds
+# The streaming attention kernels (csrc/rel_attn.hip: forward, query-major and key-major backward, bank gradient) against a float64
+# restatement on the stored operands, every error propagated to first order from the same three constants:
+#   c_acc(K) * S     every fp32 sum (a score over the hd channels of a head, the softmax denominator, o / dq over the keys, dk / dv over
+#                    the queries, a bank row over the pairs of its type -- fp32 atomics in any order for a heavy type: a sum's rounding
+#                    error does not depend on its order to first order, so the same c_acc(count) holds),
+#   C_OUT[dtype]     a stored value (stored_bound),
+#   c_fast(x)        __expf (exp2 of a scaled argument: the argument's rounding grows with |x|), the reciprocal 1 / l (c_fast(0)) and
+#                    __logf = log2(l) * ln 2 (c_fast(log l), an ABSOLUTE error: one ulp of the hardware log2's result, the product with
+#                    ln 2, and a floor of 32 eps where log l is near zero).  c_fast was defined for 1-ulp hardware exp2 and rcp;
+#                    v_log_f32 is a 1-ulp transcendental of the same unit (kernel guide, cdna_hip_programming.md Guideline 8 "Use
+#                    appropriate math precision and intrinsics", and the transcendental row of MI355X_MICROARCH.md's issue-cost table),
+#                    so no further constant is needed.
+# Softmax.  With e_s the error of a score, p_j = exp(s_j) / sum_k exp(s_k) moves by p_j (ds_j - sum_k p_k ds_k) <= p_j (e_s_j + E),
+# E = sum_k p_k e_s_k.  The kernels rescale running sums by exp(m_old - m_new) each time the maximum grows and when lanes and waves are
+# merged: a term reaches the final sum through at most nf = ceil(S / KS) + log2(G) + 4 factors __expf(a_k) whose arguments add up to
+# m - s_j = delta_j, so its relative error is sum_k c_fast(a_k) = nf * c_fast(delta_j / nf) = r_j.  The denominator adds c_acc(S) and
+# the reciprocal c_fast(0).
+# Backward.  The kernels read the STORED o (D = sum d_o o + sum w dw) and the STORED lse (p = exp(s - lse)) and w: their bounds from the
+# forward enter D and p as operand errors.  pd (the weights the key-major pass multiplies into dv) is p keep / (1 - p_drop) from that p,
+# or, when the forward returned w, w itself.  In bf16 the half ulp of o is the largest term of the whole backward: D moves by up to
+# 2^-8 sum |d_o| |o|, and every gs_ij by scale p_ij times that.
+def lse_comparable(got, ref):
+    """(got, ref) with the -inf entries of ref (fully masked rows) replaced: 0 where got is -inf as well, NaN (-> ratio inf) where not"""
+    dead = torch.isinf(ref)
+    g = torch.where(dead, torch.where(got.double() == ref, 0.0, float("nan")), got.double())
+    return g, torch.where(dead, torch.zeros_like(ref), ref)
+
+
+def rel_attn_ref(q, k, v, H, scale, mode=0, rel=None, ids=None, R=None, key_pad=None, attn_mask=None, p_drop=0.0, keep=None,
+                 d_o=None, d_w=None):
+    """float64 relation attention on the stored operands.  q [T,B,d], k / v [S,B,d]; mode 1: rel = rarb [S,T,B,2d] (key-major);
+    mode 2: rel = bank [>=R,2d] and ids [S,T,B] = relation[j,i,b] (bit 31 ignored); key_pad [S,B], attn_mask [T,S] (non-zero = masked);
+    keep [T,S,B,H] bool (the restated drop_keep) when p_drop > 0; d_o [T,B,d], d_w [T,S,B,H] or None.
+    Returns a dict: o, lse (-inf on fully masked rows), w, and with d_o: pd, gs, dq, dk, dv, d_rel (mode 1: [S,T,B,2d]; mode 2: [R,2d],
+    zero rows for types without pairs) -- plus the intermediates rel_attn_bounds needs (keys starting with '_')."""
+    T, B, d = q.shape
+    S, hd = k.shape[0], d // H
+    q5, k5 = q.double().reshape(T, 1, B, H, hd), k.double().reshape(1, S, B, H, hd)
+    v4 = v.double().reshape(S, B, H, hd)
+    full = (T, S, B, H, hd)
+    if mode == 0:
+        qa, kb, qa_abs, kb_abs = q5.expand(full), k5.expand(full), q5.abs().expand(full), k5.abs().expand(full)
+    else:
+        rows = rel.double() if mode == 1 else rel.double()[ids.long() & 0x7fffffff]
+        rows = rows.reshape(S, T, B, 2 * d).permute(1, 0, 2, 3)
+        ra, rb = rows[..., :d].reshape(full), rows[..., d:].reshape(full)
+        qa, kb, qa_abs, kb_abs = q5 + ra, k5 + rb, q5.abs() + ra.abs(), k5.abs() + rb.abs()
+    s = scale * (qa * kb).sum(-1)
+    s_abs = abs(scale) * (qa_abs * kb_abs).sum(-1)
+    dead = torch.zeros(T, S, B, 1, dtype=torch.bool, device=q.device)
+    if key_pad is not None:
+        dead = dead | (key_pad != 0).reshape(1, S, B, 1)
+    if attn_mask is not None:
+        dead = dead | (attn_mask != 0).reshape(T, S, 1, 1)
+    dead = dead.expand(T, S, B, H)
+    sm = s.masked_fill(dead, float("-inf"))
+    m = sm.amax(1, keepdim=True)
+    has = torch.isfinite(m)
+    m0 = torch.where(has, m, torch.zeros_like(m))
+    e = torch.exp(sm - m0)
+    l = e.sum(1, keepdim=True)
+    p = e / l.clamp_min(1e-300)
+    logl = torch.log(l.clamp_min(1e-300)) * has
+    lse = torch.where(has, m0 + logl, torch.full_like(m, float("-inf"))).squeeze(1)
+    kf = keep.double() * drop_scale(p_drop) if p_drop > 0 else torch.ones_like(p)
+    w = kf * p
+    o = torch.einsum("ijbh,jbhe->ibhe", w, v4).reshape(T, B, d)
+    out = dict(o=o, lse=lse, w=w, _p=p, _kf=kf, _s_abs=s_abs, _delta=torch.where(dead, torch.zeros_like(s), m0 - s), _logl=logl,
+               _m=m0, _v4=v4, _qa_abs=qa_abs, _kb_abs=kb_abs, _dims=(T, S, B, H, hd, mode), _dead=dead)
+    if d_o is None:
+        return out
+    do4 = d_o.double().reshape(T, B, H, hd)
+    dw = torch.zeros_like(w) if d_w is None else d_w.double()
+    D = (do4 * o.reshape(T, B, H, hd)).sum(-1) + (w * dw).sum(1)
+    dpv = torch.einsum("ibhe,jbhe->ijbh", do4, v4)
+    X = kf * (dpv + dw) - D[:, None]
+    gs = scale * p * X
+    out.update(pd=w, gs=gs, dq=torch.einsum("ijbh,ijbhe->ibhe", gs, kb).reshape(T, B, d),
+               dk=torch.einsum("ijbh,ijbhe->jbhe", gs, qa).reshape(S, B, d), dv=torch.einsum("ijbh,ibhe->jbhe", w, do4).reshape(S, B, d),
+               _do4=do4, _dw=dw, _D=D, _dpv=dpv, _X=X, _scale=abs(scale))
+    if mode:
+        pair = torch.cat([(gs[..., None] * kb).reshape(T, S, B, d), (gs[..., None] * qa).reshape(T, S, B, d)], -1).permute(1, 0, 2, 3)
+        if mode == 1:
+            out["d_rel"] = pair
+        else:
+            tid = (ids.long() & 0x7fffffff).reshape(-1)
+            out["d_rel"] = torch.zeros(R, 2 * d, dtype=torch.float64, device=q.device).index_add_(0, tid, pair.reshape(-1, 2 * d))
+            out["_tid"], out["_R"] = tid, R
+    return out
+
+
+def rel_attn_bounds(ref, dtype, KS, G, with_w=False):
+    """{name: elementwise bound} for every output of ``rel_attn_ref`` stored as ``dtype`` (o, dq, dk, dv, d_rel; lse, w, pd, gs are fp32).
+    KS = 4 G: the keys a workgroup takes per step, G the key groups of a wave (the kernels' geometry): they set the length nf of the
+    longest chain of rescaling factors.  The bound of lse is that of its finite entries (0 where the reference is -inf).
+    ``with_w``: the backward is handed the forward's w, and its pd is then that tensor (and carries its bound)."""
+    T, S, B, H, hd, mode = ref["_dims"]
+    F32 = torch.float32
+    p, kf, w = ref["_p"], ref["_kf"], ref["w"]
+    nf = -(-S // KS) + max(G, 1).bit_length() - 1 + 4
+    e_s = c_acc(hd) * ref["_s_abs"]
+    r = nf * c_fast(ref["_delta"] / nf)
+    rel_l = (p * (e_s + r)).sum(1, keepdim=True) + c_acc(S)
+    u_p = p * (e_s + r + rel_l + c_fast(torch.zeros(())))
+    u_w = kf * u_p + c_acc(1) * w
+    v_abs = ref["_v4"].abs()
+    u_o = (torch.einsum("ijbh,jbhe->ibhe", u_w, v_abs) + c_acc(S) * torch.einsum("ijbh,jbhe->ibhe", w, v_abs)).reshape(T, B, H * hd)
+    logl, m = ref["_logl"], ref["_m"]
+    u_lse = (rel_l + c_fast(logl) + c_acc(1) * (m.abs() + logl.abs())).squeeze(1)
+    lse_fin = torch.where(torch.isinf(ref["lse"]), torch.zeros_like(ref["lse"]), ref["lse"])
+    b = dict(o=stored_bound(ref["o"], u_o, dtype), w=stored_bound(w, u_w, F32),
+             lse=stored_bound(lse_fin, u_lse, F32) * torch.isfinite(ref["lse"]))
+    if "gs" not in ref:
+        return b
+    do_abs, dw_abs, D, X, gs, scale = ref["_do4"].abs(), ref["_dw"].abs(), ref["_D"], ref["_X"], ref["gs"], ref["_scale"]
+    o4 = ref["o"].reshape(T, B, H, hd)
+    u_D = ((do_abs * b["o"].reshape(T, B, H, hd)).sum(-1) + c_acc(hd) * (do_abs * o4.abs()).sum(-1)
+           + (b["w"] * dw_abs).sum(1) + c_acc(S) * (w * dw_abs).sum(1) + c_acc(1) * D.abs())
+    u_pb = p * (e_s + b["lse"][:, None] + c_fast(ref["_delta"] + logl))            # p again, from the stored lse
+    u_pd = u_w if with_w else kf * u_pb + c_acc(1) * w
+    dpv = ref["_dpv"]
+    u_X = (kf * (c_acc(hd) * torch.einsum("ibhe,jbhe->ijbh", do_abs, v_abs) + c_acc(1) * (dpv.abs() + dw_abs))
+           + u_D[:, None] + c_acc(1) * (kf * (dpv + ref["_dw"]).abs() + D.abs()[:, None]))
+    u_gs = scale * (u_pb * X.abs() + p * u_X) + c_acc(1) * gs.abs()
+    qa_abs, kb_abs, g_abs = ref["_qa_abs"], ref["_kb_abs"], gs.abs()
+    d = H * hd
+    u_dq = torch.einsum("ijbh,ijbhe->ibhe", u_gs + c_acc(S) * g_abs, kb_abs).reshape(T, B, d)
+    u_dk = torch.einsum("ijbh,ijbhe->jbhe", u_gs + c_acc(T) * g_abs, qa_abs).reshape(S, B, d)
+    u_dv = torch.einsum("ijbh,ibhe->jbhe", u_pd + c_acc(T) * w, do_abs).reshape(S, B, d)
+    b.update(pd=stored_bound(w, u_pd, F32), gs=stored_bound(gs, u_gs, F32), dq=stored_bound(ref["dq"], u_dq, dtype),
+             dk=stored_bound(ref["dk"], u_dk, dtype), dv=stored_bound(ref["dv"], u_dv, dtype))
+    if mode:
+        def halves(x):
+            return torch.cat([(x[..., None] * kb_abs).reshape(T, S, B, d), (x[..., None] * qa_abs).reshape(T, S, B, d)], -1).permute(1, 0, 2, 3)
+        if mode == 1:
+            b["d_rel"] = stored_bound(ref["d_rel"], halves(u_gs + c_acc(1) * g_abs), dtype)
+        else:
+            tid, R = ref["_tid"], ref["_R"]
+            zero = torch.zeros(R, 2 * d, dtype=torch.float64, device=gs.device)
+            U = zero.clone().index_add_(0, tid, halves(u_gs).reshape(-1, 2 * d))
+            Sabs = zero.index_add_(0, tid, halves(g_abs).reshape(-1, 2 * d))
+            cnt = torch.bincount(tid, minlength=R)[:R]
+            b["d_rel"] = stored_bound(ref["d_rel"], U + c_acc_of(2 * cnt)[:, None] * Sabs, dtype)      # per pair: gs k and gs RB
+    return b
